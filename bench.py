@@ -18,6 +18,12 @@ Paths (--path):
 launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  Weak scaling: every rank decodes a batch of the same shape; the only
 collective is the frame gather (one all_gather per step, asynchronous, collected one step later).
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline needs: synthesise the workload, check the frames of the
+first passes, warm up, time exactly K steps (every one fingerprint-checked against those frames), print the line.  `--full`
+adds what else the benchmark measures: the second line through the reference's shipped gradient demodulator, the CPU
+baseline, the K-step block repeated for at least 0.5 s (--min-seconds).  `--dump-outputs DIR` writes the frames of the last
+timed step (dump_frames); the workload is synthesised from fixed seeds, so the same arguments give the same inputs.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -233,6 +239,40 @@ def quoted_ceiling(sf, demod):
     return best
 
 
+# -------------------------------------------------------------------------------------------------- outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_frames(out_dir, slots, counts):
+    """--dump-outputs: the frames one step handed its caller - every rank's rows of the gathered slot block (slots uint8
+    [world, capacity, SLOT_BYTES], counts[r] rows of rank r in use) - written as arrays that two builds compare row for row:
+      frame_bytes       float32 [n, SLOT_BLOB]  the frame (loratap | PHY header | payload), zeros behind its length
+      frame_length      float32 [n]
+      frame_stream      float32 [n]             the stream index within its rank's workload
+      frame_rank        float32 [n]
+      frame_header_pos  float64 [n]             sample position of the first header symbol
+    Rows in (rank, stream, header position) order: the order in which a pass publishes its frames is not part of its result.
+    Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows (kept in that order)."""
+    from gr_lora_amd import gather
+    used = [slots[r, :n] for r, n in enumerate(counts)]
+    blk = np.concatenate(used) if used else np.zeros((0, gather.SLOT_BYTES), np.uint8)
+    rank_of = np.repeat(np.arange(len(counts)), counts)
+    head = np.ascontiguousarray(blk[:, 0:8]).view(np.uint32).reshape(-1, 2)   # stream, length
+    hpos = np.ascontiguousarray(blk[:, 8:16]).view(np.int64).reshape(-1)
+    order = np.lexsort((hpos, head[:, 0], rank_of))
+    row_bytes = 4 * gather.SLOT_BLOB + 3 * 4 + 8
+    max_rows = DUMP_LIMIT_BYTES // row_bytes
+    if order.size > max_rows:
+        order = order[np.sort(np.random.default_rng(0).choice(order.size, max_rows, replace=False))]
+    length = head[order, 1].astype(np.int64)
+    data = blk[order, 16:].astype(np.float32)
+    data[np.arange(gather.SLOT_BLOB)[None, :] >= length[:, None]] = 0.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("frame_bytes", data), ("frame_length", length.astype(np.float32)), ("frame_stream", head[order, 0].astype(np.float32)),
+                      ("frame_rank", rank_of[order].astype(np.float32)), ("frame_header_pos", hpos[order].astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 # ------------------------------------------------------------------------------------------------- launcher
 def respawn_under_launcher(n):
     """`python bench.py --gpus N` on its own: one rank per GPU under torch.distributed.run, rendezvous on 127.0.0.1"""
@@ -276,11 +316,22 @@ def main():
                     "include the time a kernel shares the device with its neighbour, and roofline.frac is computed from them)")
     ap.add_argument("--split", action="store_true", help="config 2 / 3 as ONE stream split over the ranks by sample range (SURVEY 8(e), second clause: "
                     "gr_lora_amd.gather.split_stream_ranges - margins on both sides of every cut, frames de-duplicated by header position): strong scaling")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the K-step block (--steps) is timed repeatedly, each block bracketed by barrier + synchronize on both sides, "
-                    "until the timed blocks add up to this many seconds; value / ms_per_step are the MEDIAN block's (0: one block)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-grad-line", action="store_true", help="skip the second measurement (the reference's shipped gradient demodulator on the same workload)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="the K-step block (--steps) is timed repeatedly, each block bracketed by barrier + synchronize on both sides, "
+                    "until the timed blocks add up to this many seconds; value / ms_per_step are the MEDIAN block's (0: one block, exactly --steps timed steps; "
+                    "default 0, with --full 0.5)")
+    ap.add_argument("--full", action="store_true", help="also the measurements the headline does not need: the second line through the reference's shipped gradient "
+                    "demodulator, the CPU baseline, repeated timed blocks (--min-seconds), and on --path work / mux their side figures (H2D bandwidth, one handle per channel)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-grad-line", action="store_true", help="with --full: skip the second measurement (the reference's shipped gradient demodulator on the same workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--path device: after the timed steps, write the frames the last timed step handed its caller "
+                    "as DIR/<name>.npy (float32 / float64; see dump_frames)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.min_seconds is None:
+        args.min_seconds = 0.5 if args.full else 0.0
+    if args.dump_outputs is not None and args.path != "device":
+        ap.error("--dump-outputs: --path device only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_launcher(args.gpus)
@@ -483,19 +534,20 @@ def main():
                 x ^= int(np.bitwise_xor.reduce(np.ascontiguousarray(slots[r, :n]).reshape(-1).view(np.uint64)))
         return (tuple(counts), x)
     want_fp = fingerprint(kept[-1]) if kept else None
-    step_fp = {"n": 0, "bad": 0}
+    step_fp = {"n": 0, "bad": 0, "last": None}
 
     def check_step(done):
         step_fp["n"] += 1
+        step_fp["last"] = done   # (--dump-outputs: the block of the last timed step)
         if want_fp is None or fingerprint(done) != want_fp:
             step_fp["bad"] += 1
 
     run(40 if n_items < 4e8 else 4)   # pre-roll, untimed like the check above: brings the device to its sustained clocks
     run(args.warmup)                  # the W warm-up steps proper
     # The timed region: EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks.  A block of 20 passes of the
-    # default workload is 9 ms - too short for anything outside this process to see the device busy - so the block is repeated (every
-    # block bracketed the same way, every step of every block fingerprint-checked) until the blocks add up to --min-seconds; the line
-    # reports the MEDIAN block (`timed_blocks`, `timed_region_s`, `block_ms_min` / `_max` say what was run).
+    # default workload is 9 ms - too short for anything outside this process to see the device busy - so with --min-seconds (default
+    # with --full) the block is repeated (every block bracketed the same way, every step of every block fingerprint-checked) until the
+    # blocks add up to that; the line reports the MEDIAN block (`timed_blocks`, `timed_region_s`, `block_ms_min` / `_max` say what was run).
     def timed_block():
         if use_dist:
             dist.barrier()
@@ -537,12 +589,14 @@ def main():
         total_items = whole_items if split_ranges is not None else n_items
         verified = verified and step_fp["bad"] == 0 and step_fp["n"] == steps_timed
         verified_ranks = 0 if unverifiable else 1
+    if rank == 0 and args.dump_outputs is not None and step_fp["last"] is not None:
+        dump_frames(args.dump_outputs, *step_fp["last"])
 
     # The same workload through the reference's SHIPPED demodulator (max_frequency_gradient_idx, decoder_impl.cc:499; --demod 0
     # makes it the headline): its own kernels (walker2/3_*_grad), verified against what the compiled reference published on this IQ
-    # (tests/golden/fullsize_ref.json).  A second, shorter measurement after the timed region of the headline; single process only.
+    # (tests/golden/fullsize_ref.json).  A second, shorter measurement after the timed region of the headline; single process, --full only.
     grad_line = None
-    if rank == 0 and world == 1 and args.config in (2, 3) and args.demod != 0 and not args.no_grad_line and split_ranges is None:
+    if args.full and rank == 0 and world == 1 and args.config in (2, 3) and args.demod != 0 and not args.no_grad_line and split_ranges is None:
         try:
             fx = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_ref.json")))
             wantk = dict(sf=sf, cr=args.cr, packets=packets, payload=args.payload, streams=min(args.streams, packets), seed=(2 if args.config == 2 else 100 * sf + 4))
@@ -633,7 +687,7 @@ def main():
                                                  "note": "kernel_ms_per_pass sums kernels that overlap; see docs/LAB_NOTEBOOK.md 4.13 / 5.5"}
         if grad_line is not None:
             res["reference_default_demodulator"] = grad_line
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(cfg, iq, offs, lens)
             res["cpu_baseline"] = {"value": round(cb["grad"][0], 3), "unit": "Msamples/s", "cores": 1, "kind": "port",
                                    "sample": "oracle/lora_oracle.c (C restatement of lib/decoder_impl.cc) built -O3 -march=native on this host, reference-default gradient "
@@ -710,18 +764,22 @@ def run_mux_path(args, torch, capi, cfg, iq, offs, lens, kw, expect_all, wl):
 
     _dt, got, passes = one_mux()
     verified = all(got[c] == expect_all[c] for c in range(nch))
-    t_mux = float(np.median([one_mux()[0] for _ in range(max(3, min(args.steps, 5)))]))
-    _dt, goth = one_handles()
-    verified_h = all(goth[c] == expect_all[c] for c in range(nch))
-    t_h = float(np.median([one_handles()[0] for _ in range(3)]))
+    for _ in range(args.warmup):
+        one_mux()
+    t_mux = float(np.median([one_mux()[0] for _ in range(args.steps)]))
     n = int(sum(lens))
-    return {"metric": "IQ Msamples/s demodulated through lora_hip_mux (host buffers in, PCIe included)", "value": round(n / t_mux / 1e6, 3), "unit": "Msamples/s",
-            "n_gpus": 1, "steps": max(3, min(args.steps, 5)), "warmup": 1, "ms_per_step": round(t_mux * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": wl, "path": "mux (%d channels through one lora_hip_mux, %d items per call, device passes of %d items per channel)" % (nch, chunk, batch),
-                       "device_passes": passes, "bit_exact_vs_expected": verified},
-            "one_handle_per_channel": {"value": round(n / t_h / 1e6, 3), "unit": "Msamples/s", "bit_exact_vs_expected": verified_h,
-                                       "note": "the same channels and call pattern through %d lora_hip_work handles: one device pass per channel and chunk" % nch}}
+    res = {"metric": "IQ Msamples/s demodulated through lora_hip_mux (host buffers in, PCIe included)", "value": round(n / t_mux / 1e6, 3), "unit": "Msamples/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t_mux * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": wl, "path": "mux (%d channels through one lora_hip_mux, %d items per call, device passes of %d items per channel)" % (nch, chunk, batch),
+                      "device_passes": passes, "bit_exact_vs_expected": verified}}
+    if args.full:
+        _dt, goth = one_handles()
+        verified_h = all(goth[c] == expect_all[c] for c in range(nch))
+        t_h = float(np.median([one_handles()[0] for _ in range(3)]))
+        res["one_handle_per_channel"] = {"value": round(n / t_h / 1e6, 3), "unit": "Msamples/s", "bit_exact_vs_expected": verified_h,
+                                         "note": "the same channels and call pattern through %d lora_hip_work handles: one device pass per channel and chunk" % nch}
+    return res
 
 
 def run_work_path(args, torch, capi, cfg, iq, offs, lens, kw, expect_all, wl):
@@ -755,23 +813,29 @@ def run_work_path(args, torch, capi, cfg, iq, offs, lens, kw, expect_all, wl):
 
     _dt, got = one_pass(collect=True)
     verified = [b[15:] for b, _i in got] == expect0
-    # measured H2D bandwidth of this box out of the same memory, same call size: the ceiling of this path
-    d = torch.empty(args.chunk * 2, dtype=torch.float32, device="cuda")
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    reps = max(1, min(64, n // args.chunk))
-    for r in range(reps):
-        d.copy_(pinned[2 * r * args.chunk:2 * (r + 1) * args.chunk], non_blocking=True)
-    torch.cuda.synchronize()
-    h2d = reps * args.chunk * 8 / (time.perf_counter() - t0) / 1e9
-    times = [one_pass()[0] for _ in range(max(3, min(args.steps, 7)))]
+    h2d = None
+    if args.full:
+        # measured H2D bandwidth of this box out of the same memory, same call size: the ceiling of this path
+        d = torch.empty(args.chunk * 2, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reps = max(1, min(64, n // args.chunk))
+        for r in range(reps):
+            d.copy_(pinned[2 * r * args.chunk:2 * (r + 1) * args.chunk], non_blocking=True)
+        torch.cuda.synchronize()
+        h2d = reps * args.chunk * 8 / (time.perf_counter() - t0) / 1e9
+    for _ in range(args.warmup):
+        one_pass()
+    times = [one_pass()[0] for _ in range(args.steps)]
     dt = float(np.median(times))
-    return {"metric": "IQ Msamples/s demodulated through lora_hip_work (host buffers in, PCIe included)", "value": round(n / dt / 1e6, 3), "unit": "Msamples/s",
-            "n_gpus": 1, "steps": len(times), "warmup": 1, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": wl + "; as ONE stream of %d items" % n, "path": "work (lora_hip_work out of page-locked host memory, %d items per call, device passes of %d items)" % (args.chunk, args.batch),
-                       "frames": len(got), "bit_exact_vs_expected": verified},
-            "pcie": {"h2d_GBps_measured": round(h2d, 2), "achieved_GBps": round(8 * n / dt / 1e9, 2), "frac_of_h2d": round(8 * n / dt / 1e9 / h2d, 4)}}
+    res = {"metric": "IQ Msamples/s demodulated through lora_hip_work (host buffers in, PCIe included)", "value": round(n / dt / 1e6, 3), "unit": "Msamples/s",
+           "n_gpus": 1, "steps": len(times), "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32", "data": "synthetic",
+           "config": {"workload": wl + "; as ONE stream of %d items" % n, "path": "work (lora_hip_work out of page-locked host memory, %d items per call, device passes of %d items)" % (args.chunk, args.batch),
+                      "frames": len(got), "bit_exact_vs_expected": verified}}
+    if h2d is not None:
+        res["pcie"] = {"h2d_GBps_measured": round(h2d, 2), "achieved_GBps": round(8 * n / dt / 1e9, 2), "frac_of_h2d": round(8 * n / dt / 1e9 / h2d, 4)}
+    return res
 
 
 if __name__ == "__main__":

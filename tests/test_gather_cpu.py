@@ -178,6 +178,32 @@ def test_async_gather_single_process():
         g.submit(gather.pack_frames(frames * 3, 6))
 
 
+def test_bench_dump_frames(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the rows in use of every rank's block, in (rank, stream, header position) order, zeros behind
+    each frame's length, float32 / float64; above the size limit a seeded sample of the rows, the same on every call."""
+    import bench
+    r0 =[(b"\x01\x02\x03", 1, 500), (b"abcd", 0, 900), (b"zz", 0, 100)]
+    r1 = [(b"q" * 275, 0, 7)]
+    slots = np.stack([gather.pack_frames(r0, 4), gather.pack_frames(r1, 4)])
+    slots[0, 3] = 0xab                                    # behind rank 0's count: whatever an earlier step left there
+    slots[0, 1, 16 + 4:] = 0xcd                           # behind a frame's length
+    bench.dump_frames(str(tmp_path), slots, [3, 1])
+    out = {n: np.load(tmp_path / (n + ".npy")) for n in ("frame_bytes", "frame_length", "frame_stream", "frame_rank", "frame_header_pos")}
+    assert out["frame_bytes"].dtype == np.float32 and out["frame_bytes"].shape == (4, gather.SLOT_BLOB)
+    assert out["frame_header_pos"].dtype == np.float64 and out["frame_header_pos"].tolist() == [100, 900, 500, 7]
+    assert out["frame_stream"].tolist() == [0, 0, 1, 0] and out["frame_rank"].tolist() == [0, 0, 0, 1]
+    assert out["frame_length"].tolist() == [2, 4, 3, 275]
+    want = np.zeros((4, gather.SLOT_BLOB), np.float32)
+    for i, b in enumerate([b"zz", b"abcd", b"\x01\x02\x03", b"q" * 275]):
+        want[i, :len(b)] = np.frombuffer(b, np.uint8)
+    assert np.array_equal(out["frame_bytes"], want)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * (4 * gather.SLOT_BLOB + 20))
+    bench.dump_frames(str(tmp_path / "a"), slots, [3, 1])
+    bench.dump_frames(str(tmp_path / "b"), slots, [3, 1])
+    a, b = (np.load(tmp_path / d / "frame_header_pos.npy") for d in ("a", "b"))
+    assert a.size == 2 and np.array_equal(a, b) and list(a) == sorted(a, key=[100, 900, 500, 7].index)
+
+
 # ---- one long stream over two ranks (SURVEY 8(e), second clause): gather.split_stream_ranges / owned ----------------
 def _split_worker(rank, world, port, q):
     import numpy as np

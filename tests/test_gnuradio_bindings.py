@@ -7,9 +7,10 @@
 * shim/gnuradio/CMakeLists.txt -- the overlay build whose gnuradio-lora target links lora_hip instead of liquid
   (lib/CMakeLists.txt:41-42): configured and built with cmake in its LORA_HIP_MOCK_GNURADIO mode;
 * shim/gnuradio/grc/lora_receiver_hip.block.yml -- the GRC definition: same block id, parameters, make template and
-  callbacks as grc/lora_receiver.block.yml:3-88 (checked against a summary committed here, and against the reference's own
-  file when /root/reference is present)."""
+  callbacks as grc/lora_receiver.block.yml:3-88 (checked against a summary committed here, and field by field against the
+  reference's own file as tests/golden/grc_lora_receiver_block.json records it)."""
 import importlib.util
+import json
 import os
 import shutil
 import subprocess
@@ -160,6 +161,6 @@ def test_grc_block_definition():
     assert y["templates"]["callbacks"] == ["set_center_freq(${center_freq})", "set_sf(${sf})"]
     assert y["inputs"] == [{"domain": "stream", "dtype": "complex"}]
     assert y["outputs"] == [{"domain": "message", "id": "frames", "optional": True}]
-    ref = "/root/reference/grc/lora_receiver.block.yml"
-    if os.path.exists(ref):   # this container only: the whole definition, field by field
-        assert _norm(y) == _norm(yaml.safe_load(open(ref)))
+    # the whole definition, field by field: the reference's grc/lora_receiver.block.yml as _norm() reads it
+    with open(os.path.join(ROOT, "tests", "golden", "grc_lora_receiver_block.json")) as f:
+        assert _norm(y) == json.load(f)

@@ -89,7 +89,8 @@ def _bench(argv, env=None):
 
 
 def test_bench_under_torchrun_world1_matches_plain_run():
-    common = ["--gpus", "1", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--packets", "1024"]
+    # (--min-seconds 0.5: the 30-step block repeated for half a second on both sides, the median block compared)
+    common = ["--gpus", "1", "--steps", "30", "--warmup", "5", "--min-seconds", "0.5", "--no-cpu-baseline", "--packets", "1024"]
     plain = _bench([sys.executable, "bench.py"] + common)
     env = _env()
     port = env.pop("MASTER_PORT")

@@ -17,5 +17,5 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats"
 CMD="python $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-grad-line --min-seconds 0 $*"
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- $CMD > "$OUT/fetch.log" 2>&1; echo "fetch rc=$?"
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- $CMD > "$OUT/write.log" 2>&1; echo "write rc=$?"
-(cd $REPO && timeout 300 python bench.py --steps $STEPS --warmup 2 ${PROFILE_LINE_FLAGS:-} $* 2>/dev/null | tail -1 > "$OUT/line.json")   # the unprofiled line (>= 0.5 s of timed blocks, median); PROFILE_LINE_FLAGS=--no-cpu-baseline: without the CPU legs
+(cd $REPO && timeout 300 python bench.py --full --steps $STEPS --warmup 2 ${PROFILE_LINE_FLAGS:-} $* 2>/dev/null | tail -1 > "$OUT/line.json")   # the unprofiled line (>= 0.5 s of timed blocks, median); PROFILE_LINE_FLAGS=--no-cpu-baseline: without the CPU legs
 tail -1 "$OUT/stats.log" | cut -c1-300
