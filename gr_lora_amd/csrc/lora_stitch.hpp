@@ -135,6 +135,34 @@ void adopt(Env &env, const AttemptRec &r, StreamDesc &sd)
 
 struct Cursor { int64_t pos; uint32_t cr; }; // DETECT state between attempts: position + carried d_phdr.cr
 
+// A job that walks stream sd from the state `from` up to `limit`; stop_at_header: a probe, which stops on entering the first header
+inline Job walk_job(const StreamDesc &sd, Cursor from, int64_t limit, bool stop_at_header)
+{
+    Job j{};
+    j.stream_off = sd.off; j.stream_len = sd.len; j.start = from.pos; j.scan_limit = limit;
+    j.stream_id = sd.id; j.cr_prev = from.cr; j.max_attempts = 0; j.stop_at_header = stop_at_header ? 1u : 0u;
+    return j;
+}
+
+inline bool debug_on() { static const bool on = getenv("LORA_HIP_DEBUG") != nullptr; return on; }
+inline bool debug_jobs_on() { static const bool on = getenv("LORA_HIP_DEBUG_JOBS") != nullptr; return on; }
+
+// LORA_HIP_DEBUG_JOBS: job k of a launch, its result and its records ([job]: segment jobs, [probe]: the probe launch, [serial]: serial walks),
+// comparable between the device and the CPU simulation
+inline void dump_job(const char *tag, size_t k, const Job &j, const RunOut &R)
+{
+    const JobResult &r = R.res[k];
+    fprintf(stderr, "[%s] %zu start %lld limit %lld probe_limit %lld cr %u | final_pos %lld cr %u n_att %u stop %u pad %u npush %u | tail %u: first %u n_att %u final_pos %lld cr %u stop %u pad %u npush %u\n",
+            tag, k, (long long)j.start, (long long)j.scan_limit, (long long)j.probe_limit, j.cr_prev, (long long)r.final_pos, r.final_cr, r.n_attempts, r.stop_reason, r.pad,
+            r.npush, r.tail_valid, r.tail_first_rec, r.tail_n_attempts, (long long)r.tail_final_pos, r.tail_final_cr, r.tail_stop_reason, r.tail_pad, r.tail_npush);
+    const uint32_t n = r.n_attempts + (r.tail_valid ? r.tail_n_attempts : 0u);
+    for (uint32_t a = 0; a < n && a < R.cap; a++) {
+        const AttemptRec &t = R.rec(k, a);
+        fprintf(stderr, "[%s]    rec %u status %u start %lld trig %lld hdr %lld end %lld nsym %u npush %u cr_prev %u ambig %u len %u\n", tag, a, t.status,
+                (long long)t.start_pos, (long long)t.trig_pos, (long long)t.hdr_pos, (long long)t.end_pos, t.n_symbols, t.npush, t.cr_prev, t.hdr_ambig, t.frame_len);
+    }
+}
+
 inline uint32_t recs_for(uint64_t span_items, uint32_t sps)
 { // a completed packet spans >= 13 symbols, a lost-sync attempt >= 5 (+ its DETECT steps)
     return (uint32_t)std::min<uint64_t>(span_items / (5ull * sps) + 6ull, 4096ull);
@@ -145,10 +173,7 @@ template <class Env>
 int run_serial(Env &env, StreamDesc &sd, Cursor &cur, int64_t limit, bool tracing)
 {
     while (true) {
-        std::vector<Job> jobs(1);
-        Job &j = jobs[0];
-        j.stream_off = sd.off; j.stream_len = sd.len; j.start = cur.pos; j.scan_limit = limit; j.stream_id = sd.id;
-        j.cr_prev = cur.cr; j.max_attempts = 0; j.stop_at_header = 0;
+        const std::vector<Job> jobs(1, walk_job(sd, cur, limit, false));
         const uint64_t span = (uint64_t)std::max<int64_t>(limit - cur.pos, 0);
         const uint32_t rpj = recs_for(span, env.sps());
         const uint32_t trace_cap = tracing ? (uint32_t)std::min<uint64_t>(2ull * (span / env.sps()) + 64ull, 1ull << 22) : 0u;
@@ -156,16 +181,7 @@ int run_serial(Env &env, StreamDesc &sd, Cursor &cur, int64_t limit, bool tracin
         int s = env.run_jobs(jobs, rpj, trace_cap, out);
         if (s != 0) return s;
         const JobResult &jr = out.res[0];
-        static const bool dbg_jobs = getenv("LORA_HIP_DEBUG_JOBS") != nullptr;
-        if (dbg_jobs) {
-            fprintf(stderr, "[serial] start %lld limit %lld cr %u | final_pos %lld cr %u n_att %u stop %u pad %u npush %u\n", (long long)j.start, (long long)j.scan_limit, j.cr_prev,
-                    (long long)jr.final_pos, jr.final_cr, jr.n_attempts, jr.stop_reason, jr.pad, jr.npush);
-            for (uint32_t a = 0; a < jr.n_attempts && a < out.cap; a++) {
-                const AttemptRec &t = out.rec(0, a);
-                fprintf(stderr, "[serial]    rec %u status %u start %lld trig %lld hdr %lld end %lld nsym %u npush %u\n", a, t.status, (long long)t.start_pos, (long long)t.trig_pos, (long long)t.hdr_pos,
-                        (long long)t.end_pos, t.n_symbols, t.npush);
-            }
-        }
+        if (debug_jobs_on()) dump_job("serial", 0, jobs[0], out);
         for (uint32_t a = 0; a < out.n_done(0); a++) adopt(env, out.rec(0, a), sd);
         if (tracing) env.append_trace(out, 0, trace_cap, sd.abs_base);
         cur.cr = jr.final_cr;
@@ -177,6 +193,60 @@ int run_serial(Env &env, StreamDesc &sd, Cursor &cur, int64_t limit, bool tracin
 }
 
 inline int cr_class(uint32_t cr) { return cr >= 3u ? 2 : (cr >= 1u ? 1 : 0); }
+
+// The header FEC branch follows the carried-in d_phdr.cr (:655): a speculative decode of header r only stands if its branch is the true one
+// (that of true_cr), or the two Hamming branches agree on this header - and class 0 (no switch case upstream: the header reads as zeros) never
+// agrees with either
+inline bool wrong_fec_branch(const AttemptRec &r, uint32_t true_cr)
+{
+    const int cj = cr_class(r.cr_prev), cl = cr_class(true_cr);
+    return cj != cl && (r.hdr_ambig || cj == 0 || cl == 0);
+}
+
+// An attempt that entered DECODE_HEADER and decoded the header: a frame, a packet the data ends in, or (with_header_only) a header-only record
+// whose payload the payload pass has not decoded yet
+inline bool header_bearing(const AttemptRec &r, bool with_header_only)
+{
+    return r.hdr_pos >= 0 && (r.status == kAttemptFrame || r.status == kAttemptOutOfData || (with_header_only && r.status == kAttemptHeaderOnly));
+}
+
+// Did r START a FIND_SFD step in the state pos / fails (position and d_corr_fails)?  That is all decoder_impl.cc:785-818 read: two trajectories
+// that pass through the same such state are one from that step on, header entry included.
+inline bool passed_sfd_state(const AttemptRec &r, int64_t pos, uint32_t fails)
+{
+    for (uint32_t z = 0; z < r.n_sfd && z < (uint32_t)kMaxSfdRec; z++)
+        if (r.sfd_pos[z] == pos && r.sfd_fails[z] == fails) return true;
+    return false;
+}
+
+// The pending record job k's tail probe stopped with (at a header, behind its first FIND_SFD step, or out of data), or null: no tail probe, no
+// attempt pending, or its record did not fit
+inline const AttemptRec *tail_probe_last(const RunOut &R, size_t k)
+{
+    const JobResult &jr = R.res[k];
+    if (!jr.tail_valid || !jr.tail_pad || jr.tail_n_attempts == 0u) return nullptr;
+    const uint32_t li = std::min(jr.tail_first_rec, R.cap) + jr.tail_n_attempts - 1u;
+    return li < R.cap ? &R.rec(k, li) : nullptr;
+}
+
+// The first of job k's completed or pending records that satisfies pred, or -1
+template <class Pred>
+int find_record(const RunOut &R, size_t k, Pred pred)
+{
+    const uint32_t nall = std::min(R.res[k].n_attempts, R.cap);
+    for (uint32_t a = 0; a < nall; a++)
+        if (pred(R.rec(k, a))) return (int)a;
+    return -1;
+}
+
+// Does a header-bearing attempt (header-only records included) of a segment job in (first, target] satisfy pred?
+template <class Pred>
+bool any_segment_record(const RunOut &R, size_t first, size_t target, Pred pred)
+{
+    for (size_t k = first + 1; k <= target; k++)
+        if (find_record(R, k, [&](const AttemptRec &r) { return header_bearing(r, true) && pred(r); }) >= 0) return true;
+    return false;
+}
 
 // Burst-aware segment plan.  `edges[i]` holds the positions where stream i goes quiet (the start of every gap between
 // bursts, ascending).  Cuts are placed only at such positions and chosen greedily so that every segment carries about
@@ -380,9 +450,7 @@ int decode_begin(Env &env, std::vector<StreamDesc> &streams, PassCtx &ctx)
     for (size_t k = 0; k < segs.size(); k++) {
         const StreamDesc &sd = streams[segs[k].stream];
         Job &j = jobs[k];
-        j.stream_off = sd.off; j.stream_len = sd.len; j.start = segs[k].b0; j.scan_limit = segs[k].b1;
-        j.stream_id = sd.id; j.cr_prev = (k == first_seg[segs[k].stream]) ? sd.cr_in : env.ctor_cr();
-        j.max_attempts = 0; j.stop_at_header = 0;
+        j = walk_job(sd, Cursor{segs[k].b0, (k == first_seg[segs[k].stream]) ? sd.cr_in : env.ctor_cr()}, segs[k].b1, false);
         // tail probe: past its own limit the job continues as the next segment's probe (same limit an explicit probe gets)
         const bool has_next = k + 1 < segs.size() && segs[k + 1].stream == segs[k].stream;
         static const bool no_tail = getenv("LORA_HIP_NO_TAIL") != nullptr; // diagnostics: separate probe jobs, as the generic kernels need
@@ -596,107 +664,361 @@ int payload_end(Env &env, const std::vector<StreamDesc> &streams, PassCtx &ctx, 
     return 1;
 }
 
+// ---- decode_end's phases: round 1b, probe planning and the repairs, probe views, the stitch of one stream
+
+// One probe per segment whose own job reached a header (and one for a header-less tail): it starts from the end state of the previous header-bearing
+// job.  job: index into the probe launch, or -1 with tail_of = the segment job whose tail probe it is.  rep_out / rep_job: the repair that runs the rest
+// of the target segment again from the probe's header, if one was planned (the launch it ran in and its index there).
+struct Probe {
+    uint32_t stream; size_t target; Cursor start; int job; int tail_of;
+    const RunOut *rep_out; size_t rep_job;
+};
+
+struct ProbePlan {
+    std::vector<Probe> probes;
+    std::vector<size_t> first_probe; // per stream, and the end
+    std::vector<Job> jobs;           // the probe launch: explicit probes, tail probes promoted to explicit ones, the tail probes' repairs
+    uint32_t rpj = 0;                // the probe launch's record capacity
+};
+
+// ---- round 1b: segment jobs that guessed the wrong header FEC branch.  A later segment's job runs with the constructor's d_phdr.cr; the true
+// one is its predecessor's last header's (:655).  Where the two are of different Hamming classes AND the two decodes of the job's first header
+// disagree (bit errors: hdr_ambig), its frames are not the true decoder's - at CR 4/5 / 4/6 under noise that is most packets - and used to cost
+// one serial launch per segment (32 ms for 16 of SF12's 256 packets).  The predecessor's tail probe has already reported the true value
+// (cr_prev of its pending record): all such jobs are run again, together, with it, and take their originals' place before anything is
+// stitched.  (The choice is checked like any other speculation: the stitch compares branch classes again.)
+template <class Env>
+int rerun_wrong_branch(Env &env, const std::vector<StreamDesc> &streams, const PassCtx &ctx, RunOut &R1)
+{
+    std::vector<Job> rjobs;
+    std::vector<size_t> rk;
+    for (size_t i = 0; i < streams.size(); i++) {
+        for (size_t k = ctx.first_seg[i] + 1; k < ctx.first_seg[i + 1]; k++) {
+            const AttemptRec *L = tail_probe_last(R1, k - 1);
+            if (!L || (L->status != kAttemptAtHeader && L->status != kAttemptAtSfd)) continue;
+            const bool at_sfd = L->status == kAttemptAtSfd;
+            if (at_sfd && L->n_sfd == 0u) continue;
+            // the job's first header-bearing attempt on the probe's trajectory
+            const int a = find_record(R1, k, [&](const AttemptRec &r) {
+                return header_bearing(r, true) && (at_sfd ? passed_sfd_state(r, L->sfd_pos[L->n_sfd - 1u], L->sfd_fails[L->n_sfd - 1u]) : r.hdr_pos == L->hdr_pos);
+            });
+            if (a < 0 || !wrong_fec_branch(R1.rec(k, (uint32_t)a), L->cr_prev)) continue;
+            Job j = ctx.jobs[k];
+            j.cr_prev = L->cr_prev;
+            rjobs.push_back(j);
+            rk.push_back(k);
+        }
+    }
+    if (rjobs.empty()) return 0;
+    RunOut &R3 = env.run_out(1);
+    R3.res.clear(); R3.recs.clear();
+    env.count_slow_path();
+    env.set_skip_payload(ctx.decoupled);
+    const int s = env.run_jobs(rjobs, ctx.rpj1, 0, R3);
+    if (s != 0) return s;
+    for (size_t q = 0; q < rk.size(); q++) {
+        const JobResult &nr = R3.res[q];
+        const uint32_t n = nr.n_attempts + (nr.tail_valid ? nr.tail_n_attempts : 0u);
+        if (n > R1.rpj || n > R3.cap) continue; // (does not fit the original's row: the original stands, the stitch falls back)
+        R1.res[rk[q]] = nr;
+        for (uint32_t a = 0; a < n; a++) R1.recs[rk[q] * R1.rpj + a] = R3.rec(q, a);
+    }
+    if (debug_on()) fprintf(stderr, "[lora_hip] %zu segment job(s) run again with the header FEC branch their predecessor's tail probe reported\n", rjobs.size());
+    return 0;
+}
+
+// The one repair planner.  L: the record probe `pb` stopped with.  With any noise over the stream detect_upchirp's tie between adjacent shifts is
+// decided by the noise, differently for two DETECT alignments: the speculative job then sits ONE sample beside the true trajectory, at about every
+// second cut.  Walking such a segment serially, one workgroup at a time, is what a pass would then spend its time on (round 6: 263 -> 5 Gsamples/s
+// at a noise floor 60 dB down); instead, where the probe reached a header NO segment job of its chain entered at the same sample, the REST of the
+// target segment's job is run again from the true header - Job.start_at_header, the true d_phdr.cr, the job's own limits and tail probe.  The stitch adopts a repair's records as the true trajectory (which they
+// are); where its end state is the speculative job's - fine_sync pulls the two together within a packet - the chain goes on, else the next cut's
+// check falls back as before.  Appends the repair to `launch`, which runs into `out`; false: nothing to repair.
+inline bool plan_repair(const PassCtx &ctx, const RunOut &R1, const StreamDesc &sd, const AttemptRec &L, Probe &pb, std::vector<Job> &launch,
+                        const RunOut &out)
+{
+    if (L.status != kAttemptAtHeader || L.hdr_pos < 0) return false;
+    // (header-only records count: a decoupled pass ahead of its payload_end.  Where a job did enter it, the stitch's own match - with its
+    // FEC-branch condition - decides)
+    if (any_segment_record(R1, ctx.first_seg[pb.stream], pb.target, [&](const AttemptRec &r) { return r.hdr_pos == L.hdr_pos; })) return false;
+    const Job &target = ctx.jobs[pb.target];
+    Job j = walk_job(sd, Cursor{L.hdr_pos, L.cr_prev}, target.scan_limit, false);
+    j.start_at_header = 1; j.probe_limit = target.probe_limit;
+    pb.rep_out = &out;
+    pb.rep_job = launch.size();
+    launch.push_back(j);
+    return true;
+}
+
+// ---- round 2: the probes of a pass and the jobs of its probe launch, planned on R1 as it stands.  repair: plan repairs and whole-segment probes
+// (not under tracing or LORA_HIP_NO_REPAIR); R2: where the probe launch will put its results.
+inline void plan_probes(uint32_t sps, const std::vector<StreamDesc> &streams, const PassCtx &ctx, const RunOut &R1, const RunOut &R2, bool repair,
+                        ProbePlan &plan)
+{
+    const std::vector<Seg> &segs = ctx.segs;
+    std::vector<Probe> &probes = plan.probes;
+    probes.clear(); plan.jobs.clear();
+    plan.first_probe.assign(streams.size() + 1, 0);
+    auto has_header = [&](size_t k) { return find_record(R1, k, [](const AttemptRec &r) { return header_bearing(r, true); }) >= 0; };
+    auto job_ok = [&](size_t k) { return !R1.res[k].pad && R1.res[k].stop_reason != 2u; };
+    // Probes along the speculative chain.  Only segments whose own job reached a header get a probe; it starts from the end state of the previous
+    // header-bearing job and scans through any header-less segments in between.
+    for (size_t i = 0; i < streams.size(); i++) {
+        plan.first_probe[i] = probes.size();
+        const size_t f = ctx.first_seg[i], e = ctx.first_seg[i + 1];
+        if (e - f < 2) continue;
+        const StreamDesc &sd = streams[i];
+        bool chain = job_ok(f), pending = false;
+        Cursor cur{R1.res[f].final_pos, R1.res[f].final_cr};
+        size_t cur_job = f; // the job whose end state `cur` is
+        auto add_probe = [&](size_t target, int64_t limit) {
+            const bool tail = R1.res[cur_job].tail_valid && ctx.jobs[cur_job].probe_limit == limit; // that job has already run this probe
+            probes.push_back(Probe{(uint32_t)i, target, cur, tail ? -1 : (int)plan.jobs.size(), tail ? (int)cur_job : -1, nullptr, 0});
+            if (!tail) plan.jobs.push_back(walk_job(sd, cur, limit, true));
+        };
+        for (size_t k = f + 1; k < e && chain; k++) {
+            if (cur.pos >= segs[k].b1) continue; // a packet ran across this whole segment
+            if (!has_header(k)) { pending = true; continue; }
+            add_probe(k, std::min<int64_t>((int64_t)sd.len, segs[k].b1 + 16ll * sps));
+            chain = job_ok(k);
+            cur = Cursor{R1.res[k].final_pos, R1.res[k].final_cr};
+            cur_job = k;
+            pending = false;
+        }
+        if (chain && pending) add_probe(e - 1, (int64_t)sd.len); // header-less tail still has to be walked
+    }
+    plan.first_probe[streams.size()] = probes.size();
+    // Tail probes that stopped behind their first FIND_SFD step (Job.tail_stop_sfd) in a state NO header-bearing attempt of their successors
+    // passed through - the successor triggered two or more chirps later, as happens when a cut falls inside a packet train: they are run to the
+    // header after all, as explicit probe jobs in the one launch below (a mismatch must cost a probe, not a serial walk of the segment).
+    // (tail_of is set only where the job's tail_valid holds: tail_probe_last finds the record.)
+    bool through = false; // some explicit probe of this launch walks its whole target segment (it needs a segment job's record capacity)
+    for (Probe &pb : probes) {
+        if (pb.job >= 0) continue;
+        const AttemptRec *L = tail_probe_last(R1, (size_t)pb.tail_of);
+        if (!L || L->status != kAttemptAtSfd || L->n_sfd == 0u) continue;
+        const int64_t pos = L->sfd_pos[L->n_sfd - 1u];
+        const uint32_t fails = L->sfd_fails[L->n_sfd - 1u];
+        if (any_segment_record(R1, ctx.first_seg[pb.stream], pb.target, [&](const AttemptRec &r) { return passed_sfd_state(r, pos, fails); })) continue;
+        Job j = walk_job(streams[pb.stream], pb.start, ctx.jobs[(size_t)pb.tail_of].probe_limit, true);
+        if (repair) {
+            // (round 6) ... and past it: the job walks the whole target segment from the true state - the true trajectory itself, adopted by the stitch as a probe that
+            // "ended without a header" at its limit; with noise over the stream such cuts are every second one, and a probe that stops at a header one sample beside the
+            // speculative job's would send the segment down the serial path
+            j.scan_limit = ctx.jobs[pb.target].scan_limit; j.stop_at_header = 0;
+            through = true;
+        }
+        pb.job = (int)plan.jobs.size(); pb.tail_of = -1;
+        plan.jobs.push_back(j);
+    }
+    // Tail probes that reached a header no successor job entered at the same sample: repaired in the same launch, all such cuts at once.
+    plan.rpj = through ? std::max(ctx.rpj2, ctx.rpj1) : ctx.rpj2;
+    if (!repair) return;
+    for (Probe &pb : probes) {
+        if (pb.job >= 0) continue; // (an explicit probe's result is not known yet: repair_explicit_probes, behind the launch)
+        const AttemptRec *L = tail_probe_last(R1, (size_t)pb.tail_of);
+        if (L && plan_repair(ctx, R1, streams[pb.stream], *L, pb, plan.jobs, R2)) plan.rpj = std::max(plan.rpj, ctx.rpj1);
+    }
+}
+
+// ... and the same repair for EXPLICIT probes (a decoupled pass has no tail probes; the generic kernels none either): that a probe job reached a header no
+// segment job entered is known only now, so these repairs take a launch of their own - one for all of them, into R4
+template <class Env>
+int repair_explicit_probes(Env &env, const std::vector<StreamDesc> &streams, const PassCtx &ctx, const RunOut &R1, const RunOut &R2, ProbePlan &plan,
+                           RunOut &R4)
+{
+    std::vector<Job> rjobs;
+    for (Probe &pb : plan.probes) {
+        if (pb.job < 0) continue;
+        const size_t pj = (size_t)pb.job;
+        if (!plan.jobs[pj].stop_at_header) continue; // (a probe that walks its whole target segment: nothing to match)
+        const JobResult &pr = R2.res[pj];
+        if (!pr.pad || pr.n_attempts == 0u || pr.n_attempts > R2.cap) continue;
+        plan_repair(ctx, R1, streams[pb.stream], R2.rec(pj, pr.n_attempts - 1u), pb, rjobs, R4);
+    }
+    if (rjobs.empty()) return 0;
+    env.count_probes((uint32_t)rjobs.size());
+    return env.run_jobs(rjobs, ctx.rpj1, 0, R4);
+}
+
+// One view per probe, whether it ran as its own job or as the tail of the preceding segment's job
+struct ProbeView {
+    JobResult res; const AttemptRec *recs; uint32_t cap; int64_t limit;
+    uint32_t n_done() const // attempts that ran to completion (cf. RunOut::n_done)
+    {
+        const uint32_t n = res.pad ? res.n_attempts - 1u : res.n_attempts;
+        return n < cap ? n : cap;
+    }
+};
+
+inline std::vector<ProbeView> probe_views(const PassCtx &ctx, const RunOut &R1, const RunOut &R2, const ProbePlan &plan)
+{
+    std::vector<ProbeView> pv(plan.probes.size());
+    for (size_t q = 0; q < plan.probes.size(); q++) {
+        const Probe &pb = plan.probes[q];
+        ProbeView &v = pv[q];
+        if (pb.job >= 0) {
+            const size_t pj = (size_t)pb.job;
+            v.res = R2.res[pj]; v.recs = R2.recs.data() + pj * R2.rpj; v.cap = R2.cap; v.limit = plan.jobs[pj].scan_limit;
+            continue;
+        }
+        const size_t tj = (size_t)pb.tail_of;
+        const JobResult &jr = R1.res[tj];
+        v.res = JobResult{};
+        v.res.final_pos = jr.tail_final_pos; v.res.n_attempts = jr.tail_n_attempts; v.res.final_cr = jr.tail_final_cr;
+        v.res.npush = jr.tail_npush;
+        for (int t = 0; t < 4; t++) v.res.push_tail[t] = jr.tail_push_tail[t];
+        v.res.stop_reason = jr.tail_stop_reason; v.res.pad = jr.tail_pad;
+        const uint32_t first = std::min(jr.tail_first_rec, R1.cap);
+        v.recs = R1.recs.data() + tj * R1.rpj + first; v.cap = R1.cap - first; v.limit = ctx.jobs[tj].probe_limit;
+    }
+    return pv;
+}
+
+// Adopts run `job` of R from its header record `a` on, where the probe's pending record L reached that header: the true DETECT scan is the probe's
+// (its pushes, and the SNR at the trigger, :756), the header record and everything behind it the run's.  publish_any: publish the header record as
+// it is (a merge with a segment job: the matched record is a frame); else only if it is a frame (a repair's first record).  False: the run ends with
+// an attempt pending, the stream is incomplete.
+template <class Env>
+bool adopt_from_header(Env &env, StreamDesc &sd, Cursor &cur, const AttemptRec &L, const RunOut &R, size_t job, uint32_t a, bool publish_any)
+{
+    sd.pwr.apply(L.npush, L.push_tail);
+    sd.pwr.determine_snr();
+    if (publish_any || R.rec(job, a).status == kAttemptFrame) env.publish(R.rec(job, a), sd);
+    for (uint32_t b = a + 1u; b < R.n_done(job); b++) adopt(env, R.rec(job, b), sd);
+    const JobResult &jr = R.res[job];
+    cur = Cursor{jr.final_pos, jr.final_cr};
+    if (jr.pad) { sd.incomplete = true; return false; }
+    sd.pwr.apply(jr.npush, jr.push_tail);
+    return true;
+}
+
+// ---- the stitch of stream i, probe by probe: merge with the segment job that entered the probe's header, adopt a repair, or walk serially
+template <class Env>
+int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const RunOut &R1, const ProbePlan &plan, const std::vector<ProbeView> &pv)
+{
+    const uint32_t sps = env.sps();
+    const std::vector<Seg> &segs = ctx.segs;
+    const size_t f = ctx.first_seg[i];
+    // the first segment starts from the true state: adopt it wholesale
+    for (uint32_t a = 0; a < R1.n_done(f); a++) adopt(env, R1.rec(f, a), sd);
+    if (ctx.tracing) env.append_trace(R1, (uint32_t)f, ctx.trace_cap, sd.abs_base);
+    Cursor cur{R1.res[f].final_pos, R1.res[f].final_cr};
+    int64_t covered = segs[f].b1; // the true trajectory is known up to here
+    if (R1.res[f].pad) sd.incomplete = true;
+    else sd.pwr.apply(R1.res[f].npush, R1.res[f].push_tail);
+    auto serial_to = [&](int64_t limit, const char *why) -> int {
+        if (debug_on()) fprintf(stderr, "[lora_hip] serial fallback stream %u pos %lld -> %lld: %s\n", sd.id, (long long)cur.pos, (long long)limit, why);
+        env.count_slow_path();
+        int r = run_serial(env, sd, cur, limit, false);
+        covered = std::max(covered, limit);
+        return r;
+    };
+    if (!sd.incomplete && R1.res[f].stop_reason == 2u)
+        if (const int r = serial_to(segs[f].b1, "first segment out of records")) return r;
+    for (size_t q = plan.first_probe[i]; q < plan.first_probe[i + 1] && !sd.incomplete; q++) {
+        const Probe &pb = plan.probes[q];
+        const int64_t b1 = segs[pb.target].b1;
+        if (cur.pos >= b1) continue;
+        if (pb.start.pos != cur.pos || pb.start.cr != cur.cr) { // speculation chain broken: redo serially
+            if (const int r = serial_to(b1, "probe start differs from the true state")) return r;
+            continue;
+        }
+        const ProbeView &view = pv[q];
+        const JobResult &pr = view.res;
+        // lost-sync attempts the true trajectory went through before the header
+        for (uint32_t a = 0; a < view.n_done(); a++) adopt(env, view.recs[a], sd);
+        if (!pr.pad) { // no header before the probe's limit
+            cur = Cursor{pr.final_pos, pr.final_cr};
+            sd.pwr.apply(pr.npush, pr.push_tail);
+            covered = std::max(covered, std::min<int64_t>(view.limit, b1));
+            if (pr.stop_reason == 2u || (cur.pos < b1 && cur.pos + 2 * (int64_t)sps <= (int64_t)sd.len))
+                if (const int r = serial_to(b1, "probe ended without a header")) return r;
+            continue;
+        }
+        if (pr.n_attempts > view.cap) { // the pending attempt's record did not fit
+            if (const int r = serial_to(b1, "probe out of records")) return r;
+            continue;
+        }
+        const AttemptRec &L = view.recs[pr.n_attempts - 1u];
+        if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header
+            cur.pos = L.start_pos;
+            sd.incomplete = true;
+            break;
+        }
+        // which segment job entered a header at the same sample?  (A probe that stopped behind its first FIND_SFD step, Job.tail_stop_sfd:
+        // which job's header-bearing attempt STARTED a FIND_SFD step in the state the probe stopped in - passed_sfd_state.)
+        const bool at_sfd = L.status == kAttemptAtSfd;
+        const int64_t probe_sfd_pos = (at_sfd && L.n_sfd) ? L.sfd_pos[L.n_sfd - 1u] : -1;
+        const uint32_t probe_sfd_fails = (at_sfd && L.n_sfd) ? L.sfd_fails[L.n_sfd - 1u] : 0u;
+        int match = -1;
+        size_t mk = 0;
+        for (size_t k = f + 1; k <= pb.target && match < 0; k++) {
+            if (segs[k].b1 <= cur.pos) continue;
+            mk = k;
+            match = find_record(R1, k, [&](const AttemptRec &r) { // (not a header-only record: a merge publishes the matched record's frame)
+                return header_bearing(r, false) && (at_sfd ? passed_sfd_state(r, probe_sfd_pos, probe_sfd_fails) : r.hdr_pos == L.hdr_pos) &&
+                       !wrong_fec_branch(r, L.cr_prev);
+            });
+        }
+        if (match < 0 && pb.rep_out && !at_sfd) { // the rest of the target segment, run again from the true header
+            const RunOut &RR = *pb.rep_out;
+            const size_t rj = pb.rep_job;
+            if (RR.n_done(rj) >= 1u && RR.rec(rj, 0).hdr_pos == L.hdr_pos && RR.res[rj].stop_reason != 2u) {
+                if (!adopt_from_header(env, sd, cur, L, RR, rj, 0, false)) break;
+                covered = std::max(covered, b1);
+                env.count_repair();
+                continue;
+            }
+        }
+        if (match < 0) {
+            if (debug_on()) {
+                fprintf(stderr, "[lora_hip] probe for segment %zu [%lld, %lld): start %lld cr %u -> trig %lld hdr %lld (stopped %s, FIND_SFD state %lld / %u)\n", pb.target, (long long)segs[pb.target].b0, (long long)b1,
+                        (long long)pb.start.pos, pb.start.cr, (long long)L.trig_pos, (long long)L.hdr_pos, at_sfd ? "behind its first FIND_SFD step" : "at the header", (long long)probe_sfd_pos, probe_sfd_fails);
+                for (size_t k = pb.target ? pb.target - 1 : 0; k <= pb.target; k++)
+                    for (uint32_t a = 0; a < std::min(R1.res[k].n_attempts, R1.cap); a++) {
+                        const AttemptRec &r = R1.rec(k, a);
+                        fprintf(stderr, "[lora_hip]    job %zu [%lld, %lld) rec %u status %u start %lld trig %lld hdr %lld end %lld\n", k, (long long)segs[k].b0, (long long)segs[k].b1, a, r.status,
+                                (long long)r.start_pos, (long long)r.trig_pos, (long long)r.hdr_pos, (long long)r.end_pos);
+                    }
+            }
+            cur = Cursor{L.start_pos, L.cr_prev};
+            if (const int r = serial_to(b1, at_sfd ? "no segment job passed through the probe's FIND_SFD state" : "no segment job entered the same header")) return r;
+            continue;
+        }
+        if (R1.rec(mk, (uint32_t)match).status == kAttemptOutOfData) {
+            cur = Cursor{L.start_pos, L.cr_prev};
+            sd.incomplete = true;
+            break;
+        }
+        // merged: the true DETECT scan is the probe's, everything after the header is the job's
+        if (!adopt_from_header(env, sd, cur, L, R1, mk, (uint32_t)match, true)) break;
+        covered = std::max(covered, segs[mk].b1);
+        if (R1.res[mk].stop_reason == 2u)
+            if (const int r = serial_to(segs[mk].b1, "segment job out of records")) return r;
+    }
+    // whatever the probes did not cover is walked serially (exactness before speed)
+    if (!sd.incomplete && cur.pos < (int64_t)sd.len && covered < (int64_t)sd.len && cur.pos + 2 * (int64_t)sps <= (int64_t)sd.len)
+        if (const int r = serial_to((int64_t)sd.len, "uncovered tail")) return r;
+    sd.final_pos = cur.pos;
+    sd.cr_out = cur.cr;
+    return 0;
+}
+
 template <class Env>
 int decode_end(Env &env, std::vector<StreamDesc> &streams, PassCtx &ctx)
 {
     if (!ctx.launched) return 0; // nothing to decode
     ctx.launched = false;
-    const uint32_t sps = env.sps();
-    const bool tracing = ctx.tracing, segmenting = ctx.segmenting;
-    const std::vector<Seg> &segs = ctx.segs;
-    const std::vector<size_t> &first_seg = ctx.first_seg;
-    const std::vector<Job> &jobs = ctx.jobs;
-    const uint32_t rpj1 = ctx.rpj1, rpj2 = ctx.rpj2, trace_cap = ctx.trace_cap;
-    const auto tp_in = ctx.tp_in, tp0 = ctx.tp0;
-    (void)segmenting;
-    RunOut &R1 = env.run_out(0);
-    static const bool dbg_t = getenv("LORA_HIP_DEBUG") != nullptr;
+    RunOut &R1 = env.run_out(0), &R2 = env.run_out(1);
     int s = env.run_jobs_end(R1);
     if (s != 0) return s;
     const auto tp1 = std::chrono::steady_clock::now();
-    static const bool dbg_jobs = getenv("LORA_HIP_DEBUG_JOBS") != nullptr;
-    if (dbg_jobs) { // diagnostics: every segment job's result, comparable between the device and the CPU simulation
-        for (size_t k = 0; k < jobs.size(); k++) {
-            const JobResult &r = R1.res[k];
-            fprintf(stderr, "[job] %zu start %lld limit %lld probe_limit %lld | final_pos %lld cr %u n_att %u stop %u pad %u npush %u | tail %u: first %u n_att %u final_pos %lld cr %u stop %u pad %u npush %u\n",
-                    k, (long long)jobs[k].start, (long long)jobs[k].scan_limit, (long long)jobs[k].probe_limit, (long long)r.final_pos, r.final_cr, r.n_attempts, r.stop_reason, r.pad,
-                    r.npush, r.tail_valid, r.tail_first_rec, r.tail_n_attempts, (long long)r.tail_final_pos, r.tail_final_cr, r.tail_stop_reason, r.tail_pad, r.tail_npush);
-            const uint32_t n = r.n_attempts + (r.tail_valid ? r.tail_n_attempts : 0u);
-            for (uint32_t a = 0; a < n && a < R1.cap; a++) {
-                const AttemptRec &t = R1.rec(k, a);
-                fprintf(stderr, "[job]    rec %u status %u start %lld trig %lld hdr %lld end %lld nsym %u npush %u cr_prev %u ambig %u len %u\n", a, t.status, (long long)t.start_pos,
-                        (long long)t.trig_pos, (long long)t.hdr_pos, (long long)t.end_pos, t.n_symbols, t.npush, t.cr_prev, t.hdr_ambig, t.frame_len);
-            }
-        }
-    }
-    // ---- round 2: probes along the speculative chain.  Only segments whose own job
-    // reached a header get a probe; it starts from the end state of the previous
-    // header-bearing job and scans through any header-less segments in between.
-    auto has_header = [&](size_t k) {
-        const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-        for (uint32_t a = 0; a < nall; a++) {
-            const AttemptRec &r = R1.rec(k, a);
-            if (r.hdr_pos >= 0 && (r.status == kAttemptFrame || r.status == kAttemptOutOfData || r.status == kAttemptHeaderOnly)) return true;
-        }
-        return false;
-    };
-    auto job_ok = [&](size_t k) { return !R1.res[k].pad && R1.res[k].stop_reason != 2u; };
-    // ---- round 1b: segment jobs that guessed the wrong header FEC branch.  A later segment's job runs with the constructor's d_phdr.cr; the true
-    // one is its predecessor's last header's (:655).  Where the two are of different Hamming classes AND the two decodes of the job's first header
-    // disagree (bit errors: hdr_ambig), its frames are not the true decoder's - at CR 4/5 / 4/6 under noise that is most packets - and used to cost
-    // one serial launch per segment (32 ms for 16 of SF12's 256 packets).  The predecessor's tail probe has already reported the true value
-    // (cr_prev of its pending record): all such jobs are run again, together, with it, and take their originals' place before anything is
-    // stitched.  (The choice is checked like any other speculation: the stitch compares branch classes again.)
-    if (segmenting) {
-        std::vector<Job> rjobs;
-        std::vector<size_t> rk;
-        for (size_t i = 0; i < streams.size(); i++) {
-            for (size_t k = first_seg[i] + 1; k < first_seg[i + 1]; k++) {
-                const JobResult &pj = R1.res[k - 1];
-                if (!pj.tail_valid || !pj.tail_pad || pj.tail_n_attempts == 0u) continue;
-                const uint32_t li = std::min(pj.tail_first_rec, R1.cap) + pj.tail_n_attempts - 1u;
-                if (li >= R1.cap) continue;
-                const AttemptRec &L = R1.rec(k - 1, li);
-                if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) continue;
-                const bool at_sfd = L.status == kAttemptAtSfd;
-                if (at_sfd && L.n_sfd == 0u) continue;
-                bool wrong = false, right = false;
-                const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-                for (uint32_t a = 0; a < nall; a++) {
-                    const AttemptRec &r = R1.rec(k, a);
-                    if (r.hdr_pos < 0 || (r.status != kAttemptFrame && r.status != kAttemptOutOfData && r.status != kAttemptHeaderOnly)) continue;
-                    bool same = !at_sfd && r.hdr_pos == L.hdr_pos;
-                    if (at_sfd)
-                        for (uint32_t z = 0; z < r.n_sfd && z < (uint32_t)kMaxSfdRec; z++)
-                            same = same || (r.sfd_pos[z] == L.sfd_pos[L.n_sfd - 1u] && r.sfd_fails[z] == L.sfd_fails[L.n_sfd - 1u]);
-                    if (!same) continue;
-                    const int cj = cr_class(r.cr_prev), cl = cr_class(L.cr_prev);
-                    if (cj != cl && (r.hdr_ambig || cj == 0 || cl == 0)) wrong = true; else right = true;
-                    break;
-                }
-                if (!wrong || right) continue;
-                Job j = jobs[k];
-                j.cr_prev = L.cr_prev;
-                rjobs.push_back(j);
-                rk.push_back(k);
-            }
-        }
-        if (!rjobs.empty()) {
-            RunOut &R3 = env.run_out(1);
-            R3.res.clear(); R3.recs.clear();
-            env.count_slow_path();
-            env.set_skip_payload(ctx.decoupled);
-            s = env.run_jobs(rjobs, rpj1, 0, R3);
-            if (s != 0) return s;
-            for (size_t q = 0; q < rk.size(); q++) {
-                const JobResult &nr = R3.res[q];
-                const uint32_t n = nr.n_attempts + (nr.tail_valid ? nr.tail_n_attempts : 0u);
-                if (n > R1.rpj || n > R3.cap) continue; // (does not fit the original's row: the original stands, the stitch falls back)
-                R1.res[rk[q]] = nr;
-                for (uint32_t a = 0; a < n; a++) R1.recs[rk[q] * R1.rpj + a] = R3.rec(q, a);
-            }
-            if (dbg_t) fprintf(stderr, "[lora_hip] %zu segment job(s) run again with the header FEC branch their predecessor's tail probe reported\n", rjobs.size());
-        }
+    if (debug_jobs_on()) // diagnostics: every segment job's result
+        for (size_t k = 0; k < ctx.jobs.size(); k++) dump_job("job", k, ctx.jobs[k], R1);
+    if (ctx.segmenting) {
+        s = rerun_wrong_branch(env, streams, ctx, R1);
+        if (s != 0) return s;
     }
     // the payloads of the header-only jobs: the payload pass starts here and is collected behind the launch of the explicit probes below - which are
     // planned on the records as they stand (a header-only record says where its packet ends if nothing moves the symbol clock) and planned again in the
@@ -712,369 +1034,42 @@ int decode_end(Env &env, std::vector<StreamDesc> &streams, PassCtx &ctx)
         pguard.armed = pround.open; // (a pass without a header-only record launched nothing: no stream to drain, and the staging vectors keep their capacity)
     }
     env.set_skip_payload(false);
-    struct Probe { uint32_t stream; size_t target; Cursor start; int job; int tail_of; }; // job: index into pjobs, or -1 with tail_of = the job whose tail it is
-    std::vector<Probe> probes;
-    std::vector<size_t> first_probe(streams.size() + 1, 0);
-    std::vector<Job> pjobs;
-    std::vector<int> repair_of; // per probe: index into pjobs of the job that runs the rest of its target segment again from the true header, or -1
     static const bool no_repair = getenv("LORA_HIP_NO_REPAIR") != nullptr; // (A/B: every mismatching cut takes the serial path, as until round 6)
-    RunOut &R2 = env.run_out(1);
-    for (int planning = 0; planning < 2; planning++) {
-    probes.clear(); pjobs.clear();
-    first_probe.assign(streams.size() + 1, 0);
-    for (size_t i = 0; i < streams.size(); i++) {
-        first_probe[i] = probes.size();
-        const size_t f = first_seg[i], e = first_seg[i + 1];
-        if (e - f < 2) continue;
-        const StreamDesc &sd = streams[i];
-        bool chain = job_ok(f), pending = false;
-        Cursor cur{R1.res[f].final_pos, R1.res[f].final_cr};
-        size_t cur_job = f; // the job whose end state `cur` is
-        auto add_probe = [&](size_t target, int64_t limit) {
-            if (R1.res[cur_job].tail_valid && jobs[cur_job].probe_limit == limit) { // that job has already run this probe
-                probes.push_back(Probe{(uint32_t)i, target, cur, -1, (int)cur_job});
-                return;
-            }
-            Job j{};
-            j.stream_off = sd.off; j.stream_len = sd.len; j.start = cur.pos; j.scan_limit = limit;
-            j.stream_id = sd.id; j.cr_prev = cur.cr; j.max_attempts = 0; j.stop_at_header = 1;
-            probes.push_back(Probe{(uint32_t)i, target, cur, (int)pjobs.size(), -1});
-            pjobs.push_back(j);
-        };
-        for (size_t k = f + 1; k < e && chain; k++) {
-            if (cur.pos >= segs[k].b1) continue; // a packet ran across this whole segment
-            if (!has_header(k)) { pending = true; continue; }
-            add_probe(k, std::min<int64_t>((int64_t)sd.len, segs[k].b1 + 16ll * sps));
-            chain = job_ok(k);
-            cur = Cursor{R1.res[k].final_pos, R1.res[k].final_cr};
-            cur_job = k;
-            pending = false;
+    const bool repair = !ctx.tracing && !no_repair;
+    ProbePlan plan;
+    while (true) {
+        plan_probes(env.sps(), streams, ctx, R1, R2, repair, plan);
+        R2.res.clear(); R2.recs.clear();
+        if (!plan.jobs.empty()) {
+            env.count_probes((uint32_t)plan.jobs.size());
+            s = env.run_jobs(plan.jobs, plan.rpj, 0, R2);
+            if (s != 0) return s;
         }
-        if (chain && pending) add_probe(e - 1, (int64_t)sd.len); // header-less tail still has to be walked
+        if (!pround.open) break;
+        s = payload_end(env, streams, ctx, R1, pround); // from here on the records are ordinary ones
+        if (s < 0) return s;
+        pguard.armed = false;
+        if (s == 0) break; // (1: the pass was re-laid - its probes are planned again)
     }
-    first_probe[streams.size()] = probes.size();
-    // Tail probes that stopped behind their first FIND_SFD step (Job.tail_stop_sfd) in a state NO header-bearing attempt of their successors
-    // passed through - the successor triggered two or more chirps later, as happens when a cut falls inside a packet train: they are run to the
-    // header after all, as explicit probe jobs in the one launch below (a mismatch must cost a probe, not a serial walk of the segment).
-    bool through = false; // some explicit probe of this launch walks its whole target segment (it needs a segment job's record capacity)
-    for (size_t q = 0; q < probes.size(); q++) {
-        if (probes[q].job >= 0) continue;
-        const size_t tj = (size_t)probes[q].tail_of;
-        const JobResult &jr = R1.res[tj];
-        if (!jr.tail_pad || jr.tail_n_attempts == 0u) continue;
-        const uint32_t li = std::min(jr.tail_first_rec, R1.cap) + jr.tail_n_attempts - 1u;
-        if (li >= R1.cap) continue;
-        const AttemptRec &L = R1.rec(tj, li);
-        if (L.status != kAttemptAtSfd || L.n_sfd == 0u) continue;
-        const int64_t ppos = L.sfd_pos[L.n_sfd - 1u];
-        const uint32_t pfails = L.sfd_fails[L.n_sfd - 1u];
-        bool shared = false;
-        for (size_t k = first_seg[probes[q].stream] + 1; k <= probes[q].target && !shared; k++) {
-            const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-            for (uint32_t a = 0; a < nall && !shared; a++) {
-                const AttemptRec &r = R1.rec(k, a);
-                if (r.hdr_pos < 0 || (r.status != kAttemptFrame && r.status != kAttemptOutOfData && r.status != kAttemptHeaderOnly)) continue;
-                for (uint32_t z = 0; z < r.n_sfd && z < (uint32_t)kMaxSfdRec; z++) shared = shared || (r.sfd_pos[z] == ppos && r.sfd_fails[z] == pfails);
-            }
-        }
-        if (shared) continue;
-        const StreamDesc &sd = streams[probes[q].stream];
-        Job j{};
-        j.stream_off = sd.off; j.stream_len = sd.len; j.start = probes[q].start.pos; j.scan_limit = jobs[tj].probe_limit;
-        j.stream_id = sd.id; j.cr_prev = probes[q].start.cr; j.max_attempts = 0; j.stop_at_header = 1;
-        if (!tracing && !no_repair) {
-            // (round 6) ... and past it: the job walks the whole target segment from the true state - the true trajectory itself, adopted by the stitch as a probe that
-            // "ended without a header" at its limit; with noise over the stream such cuts are every second one, and a probe that stops at a header one sample beside the
-            // speculative job's would send the segment down the serial path
-            j.scan_limit = jobs[probes[q].target].scan_limit; j.stop_at_header = 0;
-            through = true;
-        }
-        probes[q].job = (int)pjobs.size(); probes[q].tail_of = -1;
-        pjobs.push_back(j);
-    }
-    // Tail probes that reached a header NO successor job entered at the same sample.  With any noise over the stream detect_upchirp's tie between adjacent
-    // shifts is decided by the noise, differently for two DETECT alignments: the speculative job then sits ONE sample beside the true trajectory, at about
-    // every second cut.  Walking such a segment serially, one workgroup at a time, is what a pass would then spend its time on (round 6: 263 -> 5 Gsamples/s
-    // at a noise floor 60 dB down); instead the REST of the target segment's job is run again from the true header - Job.start_at_header, the true d_phdr.cr, the
-    // job's own limits and tail probe - all such cuts in the one launch below.  The stitch adopts a repair's records as the true trajectory (which they are); where
-    // its end state is the speculative job's - fine_sync pulls the two together within a packet - the chain goes on, else the next cut's check falls back as before.
-    repair_of.assign(probes.size(), -1);
-    uint32_t rpj_launch = through ? std::max(rpj2, rpj1) : rpj2;
-    if (!tracing && !no_repair) {
-        for (size_t q = 0; q < probes.size(); q++) {
-            if (probes[q].job >= 0) continue; // (an explicit probe's result is not known yet: it keeps the serial path)
-            const size_t tj = (size_t)probes[q].tail_of;
-            const JobResult &jr = R1.res[tj];
-            if (!jr.tail_pad || jr.tail_n_attempts == 0u) continue;
-            const uint32_t li = std::min(jr.tail_first_rec, R1.cap) + jr.tail_n_attempts - 1u;
-            if (li >= R1.cap) continue;
-            const AttemptRec &L = R1.rec(tj, li);
-            if (L.status != kAttemptAtHeader || L.hdr_pos < 0) continue;
-            bool entered = false;
-            for (size_t k = first_seg[probes[q].stream] + 1; k <= probes[q].target && !entered; k++) {
-                const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-                for (uint32_t a = 0; a < nall && !entered; a++) {
-                    const AttemptRec &r = R1.rec(k, a);
-                    entered = r.hdr_pos == L.hdr_pos && (r.status == kAttemptFrame || r.status == kAttemptOutOfData || r.status == kAttemptHeaderOnly); // (header-only: a decoupled pass ahead of its payload_end)
-                }
-            }
-            if (entered) continue; // (the stitch's own match - with its FEC-branch condition - decides)
-            const StreamDesc &sd = streams[probes[q].stream];
-            const Job &tjob = jobs[probes[q].target];
-            Job j{};
-            j.stream_off = sd.off; j.stream_len = sd.len; j.start = L.hdr_pos; j.start_at_header = 1; j.cr_prev = L.cr_prev;
-            j.scan_limit = tjob.scan_limit; j.probe_limit = tjob.probe_limit; j.tail_stop_sfd = 0;
-            j.stream_id = sd.id; j.max_attempts = 0; j.stop_at_header = 0;
-            repair_of[q] = (int)pjobs.size();
-            pjobs.push_back(j);
-            rpj_launch = std::max(rpj_launch, rpj1);
-        }
-    }
-    R2.res.clear(); R2.recs.clear();
-    if (!pjobs.empty()) {
-        env.count_probes((uint32_t)pjobs.size());
-        s = env.run_jobs(pjobs, rpj_launch, 0, R2);
+    RunOut R4;
+    if (repair) {
+        s = repair_explicit_probes(env, streams, ctx, R1, R2, plan, R4);
         if (s != 0) return s;
     }
-    if (!pround.open) break;
-    s = payload_end(env, streams, ctx, R1, pround); // from here on the records are ordinary ones
-    if (s < 0) return s;
-    pguard.armed = false;
-    if (s == 0) break; // (1: the pass was re-laid - its probes are planned again)
-    }
-    // ... and the same repair for EXPLICIT probes (a decoupled pass has no tail probes; the generic kernels none either): that a probe job reached a header no
-    // segment job entered is known only now, so these repairs take a launch of their own - one for all of them
-    RunOut R4;
-    std::vector<int> repair4_of(probes.size(), -1);
-    if (!tracing && !no_repair) {
-        std::vector<Job> rjobs4;
-        for (size_t q = 0; q < probes.size(); q++) {
-            if (probes[q].job < 0) continue;
-            const size_t pj = (size_t)probes[q].job;
-            if (!pjobs[pj].stop_at_header) continue; // (a probe that walks its whole target segment: nothing to match)
-            const JobResult &pr = R2.res[pj];
-            if (!pr.pad || pr.n_attempts == 0u || pr.n_attempts > R2.cap) continue;
-            const AttemptRec &L = R2.rec(pj, pr.n_attempts - 1u);
-            if (L.status != kAttemptAtHeader || L.hdr_pos < 0) continue;
-            bool entered = false;
-            for (size_t k = first_seg[probes[q].stream] + 1; k <= probes[q].target && !entered; k++) {
-                const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-                for (uint32_t a = 0; a < nall && !entered; a++) {
-                    const AttemptRec &r = R1.rec(k, a);
-                    entered = r.hdr_pos == L.hdr_pos && (r.status == kAttemptFrame || r.status == kAttemptOutOfData || r.status == kAttemptHeaderOnly);
-                }
-            }
-            if (entered) continue;
-            const StreamDesc &sd = streams[probes[q].stream];
-            const Job &tjob = jobs[probes[q].target];
-            Job j{};
-            j.stream_off = sd.off; j.stream_len = sd.len; j.start = L.hdr_pos; j.start_at_header = 1; j.cr_prev = L.cr_prev;
-            j.scan_limit = tjob.scan_limit; j.probe_limit = tjob.probe_limit; j.tail_stop_sfd = 0;
-            j.stream_id = sd.id; j.max_attempts = 0; j.stop_at_header = 0;
-            repair4_of[q] = (int)rjobs4.size();
-            rjobs4.push_back(j);
-        }
-        if (!rjobs4.empty()) {
-            env.count_probes((uint32_t)rjobs4.size());
-            s = env.run_jobs(rjobs4, rpj1, 0, R4);
-            if (s != 0) return s;
-        }
-    }
-    if (dbg_jobs) {
-        for (size_t k = 0; k < pjobs.size(); k++) {
-            const JobResult &r = R2.res[k];
-            fprintf(stderr, "[probe] %zu start %lld limit %lld cr %u | final_pos %lld cr %u n_att %u stop %u pad %u npush %u\n", k, (long long)pjobs[k].start, (long long)pjobs[k].scan_limit,
-                    pjobs[k].cr_prev, (long long)r.final_pos, r.final_cr, r.n_attempts, r.stop_reason, r.pad, r.npush);
-            for (uint32_t a = 0; a < r.n_attempts && a < R2.cap; a++) {
-                const AttemptRec &t = R2.rec(k, a);
-                fprintf(stderr, "[probe]    rec %u status %u start %lld trig %lld hdr %lld end %lld nsym %u npush %u cr_prev %u ambig %u\n", a, t.status, (long long)t.start_pos, (long long)t.trig_pos,
-                        (long long)t.hdr_pos, (long long)t.end_pos, t.n_symbols, t.npush, t.cr_prev, t.hdr_ambig);
-            }
-        }
-    }
-    // one view per probe, whether it ran as its own job or as the tail of the preceding segment's job
-    struct ProbeView { JobResult res; const AttemptRec *recs; uint32_t cap; int64_t limit; };
-    std::vector<ProbeView> pv(probes.size());
-    for (size_t q = 0; q < probes.size(); q++) {
-        ProbeView &v = pv[q];
-        if (probes[q].job >= 0) {
-            const size_t pj = (size_t)probes[q].job;
-            v.res = R2.res[pj]; v.recs = R2.recs.data() + pj * R2.rpj; v.cap = R2.cap; v.limit = pjobs[pj].scan_limit;
-        } else {
-            const size_t tj = (size_t)probes[q].tail_of;
-            const JobResult &jr = R1.res[tj];
-            v.res = JobResult{};
-            v.res.final_pos = jr.tail_final_pos; v.res.n_attempts = jr.tail_n_attempts; v.res.final_cr = jr.tail_final_cr;
-            v.res.npush = jr.tail_npush;
-            for (int t = 0; t < 4; t++) v.res.push_tail[t] = jr.tail_push_tail[t];
-            v.res.stop_reason = jr.tail_stop_reason; v.res.pad = jr.tail_pad;
-            const uint32_t first = std::min(jr.tail_first_rec, R1.cap);
-            v.recs = R1.recs.data() + tj * R1.rpj + first; v.cap = R1.cap - first; v.limit = jobs[tj].probe_limit;
-        }
-    }
-    auto pv_done = [&](const ProbeView &v) { // attempts that ran to completion (cf. RunOut::n_done)
-        const uint32_t n = v.res.pad ? v.res.n_attempts - 1u : v.res.n_attempts;
-        return n < v.cap ? n : v.cap;
-    };
-
+    if (debug_jobs_on())
+        for (size_t k = 0; k < plan.jobs.size(); k++) dump_job("probe", k, plan.jobs[k], R2);
+    const std::vector<ProbeView> pv = probe_views(ctx, R1, R2, plan);
     const auto tp2 = std::chrono::steady_clock::now();
-    // ---- stitch, stream by stream, in stream order
-    for (size_t i = 0; i < streams.size(); i++) {
-        StreamDesc &sd = streams[i];
-        const size_t f = first_seg[i];
-        // the first segment starts from the true state: adopt it wholesale
-        for (uint32_t a = 0; a < R1.n_done(f); a++) adopt(env, R1.rec(f, a), sd);
-        if (tracing) env.append_trace(R1, (uint32_t)f, trace_cap, sd.abs_base);
-        Cursor cur{R1.res[f].final_pos, R1.res[f].final_cr};
-        int64_t covered = segs[f].b1; // the true trajectory is known up to here
-        if (R1.res[f].pad) sd.incomplete = true;
-        else sd.pwr.apply(R1.res[f].npush, R1.res[f].push_tail);
-        static const bool dbg = getenv("LORA_HIP_DEBUG") != nullptr;
-        auto serial_to = [&](int64_t limit, const char *why) -> int {
-            if (dbg) fprintf(stderr, "[lora_hip] serial fallback stream %u pos %lld -> %lld: %s\n", sd.id, (long long)cur.pos, (long long)limit, why);
-            env.count_slow_path();
-            int r = run_serial(env, sd, cur, limit, false);
-            covered = std::max(covered, limit);
-            return r;
-        };
-        if (!sd.incomplete && R1.res[f].stop_reason == 2u) {
-            s = serial_to(segs[f].b1, "first segment out of records");
-            if (s != 0) return s;
-        }
-        for (size_t q = first_probe[i]; q < first_probe[i + 1] && !sd.incomplete; q++) {
-            const Probe &pb = probes[q];
-            const int64_t b1 = segs[pb.target].b1;
-            if (cur.pos >= b1) continue;
-            if (pb.start.pos != cur.pos || pb.start.cr != cur.cr) { // speculation chain broken: redo serially
-                s = serial_to(b1, "probe start differs from the true state");
-                if (s != 0) return s;
-                continue;
-            }
-            const ProbeView &view = pv[q];
-            const JobResult &pr = view.res;
-            // lost-sync attempts the true trajectory went through before the header
-            for (uint32_t a = 0; a < pv_done(view); a++) adopt(env, view.recs[a], sd);
-            if (!pr.pad) { // no header before the probe's limit
-                cur = Cursor{pr.final_pos, pr.final_cr};
-                sd.pwr.apply(pr.npush, pr.push_tail);
-                covered = std::max(covered, std::min<int64_t>(view.limit, b1));
-                if (pr.stop_reason == 2u || (cur.pos < b1 && cur.pos + 2 * (int64_t)sps <= (int64_t)sd.len)) {
-                    s = serial_to(b1, "probe ended without a header");
-                    if (s != 0) return s;
-                }
-                continue;
-            }
-            if (pr.n_attempts > view.cap) { // the pending attempt's record did not fit
-                s = serial_to(b1, "probe out of records");
-                if (s != 0) return s;
-                continue;
-            }
-            const AttemptRec &L = view.recs[pr.n_attempts - 1u];
-            if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header
-                cur.pos = L.start_pos;
-                sd.incomplete = true;
-                break;
-            }
-            // which segment job entered a header at the same sample?  (A probe that stopped behind its first FIND_SFD step, Job.tail_stop_sfd:
-            // which job's header-bearing attempt STARTED a FIND_SFD step in the state the probe stopped in - position and d_corr_fails, all
-            // that decoder_impl.cc:785-818 read: from that step on the two trajectories are one, header entry included.)
-            const bool at_sfd = L.status == kAttemptAtSfd;
-            const int64_t probe_sfd_pos = (at_sfd && L.n_sfd) ? L.sfd_pos[L.n_sfd - 1u] : -1;
-            const uint32_t probe_sfd_fails = (at_sfd && L.n_sfd) ? L.sfd_fails[L.n_sfd - 1u] : 0u;
-            int match = -1;
-            size_t mk = 0;
-            for (size_t k = f + 1; k <= pb.target && match < 0; k++) {
-                if (segs[k].b1 <= cur.pos) continue;
-                const uint32_t nall = std::min(R1.res[k].n_attempts, R1.cap);
-                for (uint32_t a = 0; a < nall; a++) {
-                    const AttemptRec &r = R1.rec(k, a);
-                    if (r.hdr_pos < 0 || (r.status != kAttemptFrame && r.status != kAttemptOutOfData)) continue;
-                    if (!at_sfd) { if (r.hdr_pos != L.hdr_pos) continue; }
-                    else {
-                        bool shared = false;
-                        for (uint32_t q = 0; q < r.n_sfd && q < (uint32_t)kMaxSfdRec; q++) shared = shared || (r.sfd_pos[q] == probe_sfd_pos && r.sfd_fails[q] == probe_sfd_fails);
-                        if (!shared) continue;
-                    }
-                    { // the header FEC branch follows the carried-in d_phdr.cr (:655): the job's speculative decode only stands
-                      // if its branch is the true one, or the two Hamming branches agree on this header - and class 0
-                      // (no switch case upstream: the header reads as zeros) never agrees with either
-                        const int cj = cr_class(r.cr_prev), cl = cr_class(L.cr_prev);
-                        if (cj != cl && (r.hdr_ambig || cj == 0 || cl == 0)) continue;
-                    }
-                    match = (int)a; mk = k;
-                    break;
-                }
-            }
-            const bool rep2 = q < repair_of.size() && repair_of[q] >= 0, rep4 = repair4_of[q] >= 0;
-            if (match < 0 && (rep2 || rep4) && !at_sfd) { // the rest of the target segment, run again from the true header
-                const RunOut &RR = rep2 ? R2 : R4;
-                const size_t rj = (size_t)(rep2 ? repair_of[q] : repair4_of[q]);
-                const JobResult &rr = RR.res[rj];
-                const uint32_t nd = RR.n_done(rj);
-                if (nd >= 1u && RR.rec(rj, 0).hdr_pos == L.hdr_pos && rr.stop_reason != 2u) {
-                    sd.pwr.apply(L.npush, L.push_tail); // the true DETECT scan is the probe's, everything from the header on the repair's
-                    sd.pwr.determine_snr();
-                    if (RR.rec(rj, 0).status == kAttemptFrame) env.publish(RR.rec(rj, 0), sd);
-                    for (uint32_t a = 1; a < nd; a++) adopt(env, RR.rec(rj, a), sd);
-                    cur = Cursor{rr.final_pos, rr.final_cr};
-                    if (rr.pad) { sd.incomplete = true; break; }
-                    sd.pwr.apply(rr.npush, rr.push_tail);
-                    covered = std::max(covered, segs[pb.target].b1);
-                    env.count_repair();
-                    continue;
-                }
-            }
-            if (match < 0) {
-                if (dbg) {
-                    fprintf(stderr, "[lora_hip] probe for segment %zu [%lld, %lld): start %lld cr %u -> trig %lld hdr %lld (stopped %s, FIND_SFD state %lld / %u)\n", pb.target, (long long)segs[pb.target].b0, (long long)segs[pb.target].b1,
-                            (long long)pb.start.pos, pb.start.cr, (long long)L.trig_pos, (long long)L.hdr_pos, at_sfd ? "behind its first FIND_SFD step" : "at the header", (long long)probe_sfd_pos, probe_sfd_fails);
-                    for (size_t k = pb.target ? pb.target - 1 : 0; k <= pb.target; k++)
-                        for (uint32_t a = 0; a < std::min(R1.res[k].n_attempts, R1.cap); a++) {
-                            const AttemptRec &r = R1.rec(k, a);
-                            fprintf(stderr, "[lora_hip]    job %zu [%lld, %lld) rec %u status %u start %lld trig %lld hdr %lld end %lld\n", k, (long long)segs[k].b0, (long long)segs[k].b1, a, r.status,
-                                    (long long)r.start_pos, (long long)r.trig_pos, (long long)r.hdr_pos, (long long)r.end_pos);
-                        }
-                }
-                cur = Cursor{L.start_pos, L.cr_prev};
-                s = serial_to(b1, at_sfd ? "no segment job passed through the probe's FIND_SFD state" : "no segment job entered the same header");
-                if (s != 0) return s;
-                continue;
-            }
-            const AttemptRec &m = R1.rec(mk, (uint32_t)match);
-            if (m.status == kAttemptOutOfData) {
-                cur = Cursor{L.start_pos, L.cr_prev};
-                sd.incomplete = true;
-                break;
-            }
-            // merged: the true DETECT scan is the probe's, everything after the header is the job's
-            sd.pwr.apply(L.npush, L.push_tail);
-            sd.pwr.determine_snr();
-            env.publish(m, sd);
-            for (uint32_t a = (uint32_t)match + 1u; a < R1.n_done(mk); a++) adopt(env, R1.rec(mk, a), sd);
-            const JobResult &jr = R1.res[mk];
-            cur = Cursor{jr.final_pos, jr.final_cr};
-            if (jr.pad) { sd.incomplete = true; break; }
-            sd.pwr.apply(jr.npush, jr.push_tail);
-            covered = std::max(covered, segs[mk].b1);
-            if (jr.stop_reason == 2u) {
-                s = serial_to(segs[mk].b1, "segment job out of records");
-                if (s != 0) return s;
-            }
-        }
-        // whatever the probes did not cover is walked serially (exactness before speed)
-        if (!sd.incomplete && cur.pos < (int64_t)sd.len && covered < (int64_t)sd.len &&
-            cur.pos + 2 * (int64_t)sps <= (int64_t)sd.len) {
-            s = serial_to((int64_t)sd.len, "uncovered tail");
-            if (s != 0) return s;
-        }
-        sd.final_pos = cur.pos;
-        sd.cr_out = cur.cr;
+    for (size_t i = 0; i < streams.size(); i++) { // stream by stream, in stream order
+        s = stitch_stream(env, streams[i], i, ctx, R1, plan, pv);
+        if (s != 0) return s;
     }
-    if (dbg_t) {
+    if (debug_on()) {
         const auto tp3 = std::chrono::steady_clock::now();
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "[lora_hip] plan %.3f ms, round1 %.3f ms (%zu jobs, rpj %u), round2 %.3f ms (%zu probe jobs, %zu tail probes), stitch %.3f ms, walker %.3f ms\n",
-                ms(tp_in, tp0), ms(tp0, tp1), jobs.size(), rpj1, ms(tp1, tp2), pjobs.size(), probes.size() - pjobs.size(), ms(tp2, tp3), env.walker_ms());
+                ms(ctx.tp_in, ctx.tp0), ms(ctx.tp0, tp1), ctx.jobs.size(), ctx.rpj1, ms(tp1, tp2), plan.jobs.size(), plan.probes.size() - plan.jobs.size(), ms(tp2, tp3),
+                env.walker_ms());
     }
     return 0;
 }

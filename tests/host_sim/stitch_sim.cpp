@@ -10,7 +10,18 @@
 using namespace lora_hip;
 
 namespace {
-struct SimFrame { std::vector<uint8_t> blob; int64_t hdr_pos; };
+struct SimFrame { std::vector<uint8_t> blob; int64_t hdr_pos; uint32_t stream; };
+
+// 64-bit FNV-1a over every call the scheduler makes, in call order: which path produced the frames, not only the frames
+struct Fingerprint {
+    uint64_t h = 14695981039346656037ull;
+    void bytes(const void *p, size_t n)
+    {
+        for (size_t i = 0; i < n; i++) { h ^= ((const uint8_t *)p)[i]; h *= 1099511628211ull; }
+    }
+    template <class T> Fingerprint &operator<<(T v) { bytes(&v, sizeof v); return *this; }
+};
+enum FpTag : uint8_t { kFpRunJobs = 1, kFpPayload, kFpSkip, kFpPlan, kFpCountJobs, kFpCountProbes, kFpCountSlow, kFpCountRepair, kFpCountPayload, kFpPublish };
 
 struct SimEnv {
     lora_oracle_t *o;
@@ -18,7 +29,8 @@ struct SimEnv {
     size_t n_items;
     uint32_t sps_, ctor_cr_, seg_symbols, slots;
     std::vector<SimFrame> frames;
-    uint32_t n_jobs = 0, n_probes = 0, n_slow = 0, n_tails = 0, n_early = 0;
+    uint32_t n_jobs = 0, n_probes = 0, n_slow = 0, n_tails = 0, n_early = 0, n_repairs = 0;
+    Fingerprint fp;
     RunOut outs[2];
     RunOut &run_out(int which) { return outs[which & 1]; }
     bool burst_plan = false;  // offer the scheduler the gaps between bursts (the device's envelope pre-pass)
@@ -30,13 +42,18 @@ struct SimEnv {
     bool skip = false;
     uint32_t n_payload = 0, n_rerun = 0;
     bool decoupled(size_t n) const { return decoupled_mode == 1 || (decoupled_mode == 2 && n <= (two_per_cu ? slots / 2u : slots)); }
-    void set_skip_payload(bool on) { skip = on; }
+    void set_skip_payload(bool on) { fp << kFpSkip << (uint8_t)on; skip = on; }
     uint32_t n_moved = 0, n_pending = 0;
-    void count_payload(uint32_t p, uint32_t m, uint32_t r) { n_payload += p; n_moved += m; n_rerun += r; }
+    void count_payload(uint32_t p, uint32_t m, uint32_t r) { fp << kFpCountPayload << p << m << r; n_payload += p; n_moved += m; n_rerun += r; }
     // the payload pass, by the oracle: the packet decoded from its header by the complete state machine - its frame, and how far from the zero-drift
     // end it ended (the device finds the same two things by demodulating the symbols on their own and following their d_fine_sync)
     void abort_payload() {}
-    int run_payload_begin(std::vector<PayloadReq> &) { return 0; }
+    int run_payload_begin(std::vector<PayloadReq> &reqs)
+    {
+        fp << kFpPayload << (uint64_t)reqs.size();
+        for (const PayloadReq &q : reqs) fp << q.start << q.hdr_pos << q.n_walk << q.cr_prev;
+        return 0;
+    }
     int run_payload_end(std::vector<PayloadReq> &reqs)
     {
         std::vector<oracle_attempt_t> tmp(2);
@@ -93,11 +110,15 @@ struct SimEnv {
         }
         return true;
     }
-    void note_plan(bool ok, size_t) { planned += ok ? 1u : 0u; }
+    void note_plan(bool ok, size_t n) { fp << kFpPlan << (uint8_t)ok << (uint64_t)n; planned += ok ? 1u : 0u; }
     int run_jobs_begin(const std::vector<Job> &jobs, uint32_t rpj, uint32_t tc, RunOut &out) { return run_jobs(jobs, rpj, tc, out); } // (no device: runs at once)
     int run_jobs_end(RunOut &) { return 0; }
-    int run_jobs(const std::vector<Job> &jobs, uint32_t rpj, uint32_t, RunOut &out)
+    int run_jobs(const std::vector<Job> &jobs, uint32_t rpj, uint32_t trace_cap, RunOut &out)
     {
+        fp << kFpRunJobs << (uint64_t)jobs.size() << rpj << trace_cap;
+        for (const Job &j : jobs)
+            fp << j.stream_off << j.stream_len << j.start << j.scan_limit << j.stream_id << j.cr_prev << j.max_attempts << j.stop_at_header
+               << j.probe_limit << j.start_at_header << j.tail_stop_sfd;
         out.rpj = rpj; out.cap = rpj;
         out.res.assign(jobs.size(), JobResult{});
         out.recs.assign(jobs.size() * (size_t)rpj, AttemptRec{});
@@ -146,21 +167,29 @@ struct SimEnv {
         f.blob[13] = lora_oracle_snr_byte(sd.pwr.snr);
         std::memcpy(f.blob.data() + 15, r.frame, r.frame_len);
         f.hdr_pos = sd.abs_base + r.hdr_pos;
+        f.stream = sd.id;
+        fp << kFpPublish << f.hdr_pos << f.blob[13] << r.frame_len;
+        fp.bytes(r.frame, r.frame_len);
         frames.push_back(std::move(f));
     }
     void append_trace(const RunOut &, uint32_t, uint32_t, int64_t) {}
-    void count_jobs(uint32_t n) { n_jobs += n; }
-    void count_probes(uint32_t n) { n_probes += n; }
-    void count_slow_path() { n_slow++; }
-    void count_repair() {}
+    void count_jobs(uint32_t n) { fp << kFpCountJobs << n; n_jobs += n; }
+    void count_probes(uint32_t n) { fp << kFpCountProbes << n; n_probes += n; }
+    void count_slow_path() { fp << kFpCountSlow; n_slow++; }
+    void count_repair() { fp << kFpCountRepair; n_repairs++; }
     double walker_ms() const { return 0.0; }
 };
 } // namespace
 
-extern "C" int stitch_sim_decode(const float *iq, size_t n_items, int sf, int ctor_cr, int crc, int reduced_rate, int demod,
-                                 uint32_t segment_symbols, uint32_t resident_slots, int tail_probes, uint8_t *out, size_t cap, int *lens,
-                                 long long *hdr_pos, int max_frames, uint32_t *stats)
+// Several streams laid back to back in iq[] (offs[i], lens[i] items), decoded in one pass; every frame is tagged with its stream
+// (stream_of, may be null) and its header position is relative to that stream.  stats: see the end of the function.
+extern "C" int stitch_sim_decode_streams(const float *iq, size_t n_items, const unsigned long long *offs, const unsigned long long *lens, int n_streams,
+                                         int sf, int ctor_cr, int crc, int reduced_rate, int demod, uint32_t segment_symbols, uint32_t resident_slots,
+                                         int tail_probes, uint8_t *out, size_t cap, int *frame_lens, long long *hdr_pos, int *stream_of, int max_frames,
+                                         uint32_t *stats)
 {
+    if (n_streams < 1 || n_streams > 32) return -4;
+    for (int i = 0; i < n_streams; i++) if (offs[i] + lens[i] > n_items) return -4;
     lora_oracle_t *o = lora_oracle_create(1e6f, 125000, (uint8_t)sf, 0, (uint8_t)ctor_cr, crc, reduced_rate, 0, demod);
     if (!o) return -1;
     SimEnv env{o, iq, n_items, lora_oracle_sps(o), (uint32_t)ctor_cr, segment_symbols, resident_slots};
@@ -170,8 +199,10 @@ extern "C" int stitch_sim_decode(const float *iq, size_t n_items, int sf, int ct
     env.decoupled_mode = (tail_probes & 8) ? 1 : (tail_probes & 16) ? 2 : 0; // 2: the device's per-pass rule (the jobs fit the device at once)
     env.two_per_cu = (tail_probes & 32) != 0;
     env.payload_force_rerun = (uint32_t)(tail_probes >> 8) & 0xffu;
-    std::vector<StreamDesc> sds(1);
-    sds[0].off = 0; sds[0].len = n_items; sds[0].id = 0; sds[0].cr_in = (uint32_t)ctor_cr; sds[0].abs_base = 0;
+    std::vector<StreamDesc> sds(n_streams);
+    for (int i = 0; i < n_streams; i++) {
+        sds[i].off = offs[i]; sds[i].len = lens[i]; sds[i].id = (uint32_t)i; sds[i].cr_in = (uint32_t)ctor_cr; sds[i].abs_base = 0;
+    }
     const int rc = decode_streams(env, sds);
     lora_oracle_destroy(o);
     if (rc != 0) return -2;
@@ -180,10 +211,25 @@ extern "C" int stitch_sim_decode(const float *iq, size_t n_items, int sf, int ct
     for (const SimFrame &f : env.frames) {
         if (n >= max_frames || used + f.blob.size() > cap) return -3;
         std::memcpy(out + used, f.blob.data(), f.blob.size());
-        lens[n] = (int)f.blob.size(); hdr_pos[n] = f.hdr_pos; used += f.blob.size(); n++;
+        frame_lens[n] = (int)f.blob.size(); hdr_pos[n] = f.hdr_pos; used += f.blob.size();
+        if (stream_of) stream_of[n] = (int)f.stream;
+        n++;
     }
-    stats[0] = env.n_jobs; stats[1] = env.n_probes; stats[2] = env.n_slow; stats[3] = sds[0].incomplete ? 1u : 0u; stats[4] = env.n_tails; stats[5] = env.planned; stats[6] = env.n_early; stats[7] = env.n_payload; stats[8] = env.n_rerun; stats[9] = env.n_moved; stats[10] = env.n_pending;
+    uint32_t incomplete = 0; // bit i: stream i ends with a pending packet
+    for (int i = 0; i < n_streams; i++) incomplete |= sds[i].incomplete ? 1u << i : 0u;
+    stats[0] = env.n_jobs; stats[1] = env.n_probes; stats[2] = env.n_slow; stats[3] = incomplete; stats[4] = env.n_tails; stats[5] = env.planned; stats[6] = env.n_early; stats[7] = env.n_payload; stats[8] = env.n_rerun; stats[9] = env.n_moved; stats[10] = env.n_pending;
+    stats[11] = env.n_repairs; stats[12] = (uint32_t)env.fp.h; stats[13] = (uint32_t)(env.fp.h >> 32);
     return n;
+}
+
+// One stream: the whole buffer.
+extern "C" int stitch_sim_decode(const float *iq, size_t n_items, int sf, int ctor_cr, int crc, int reduced_rate, int demod,
+                                 uint32_t segment_symbols, uint32_t resident_slots, int tail_probes, uint8_t *out, size_t cap, int *lens,
+                                 long long *hdr_pos, int max_frames, uint32_t *stats)
+{
+    const unsigned long long off = 0, len = n_items;
+    return stitch_sim_decode_streams(iq, n_items, &off, &len, 1, sf, ctor_cr, crc, reduced_rate, demod, segment_symbols, resident_slots, tail_probes,
+                                     out, cap, lens, hdr_pos, nullptr, max_frames, stats);
 }
 
 // plan_burst_segments on its own: edges[] holds the gap starts of all streams back to back (n_edges[i] of them for stream i);

@@ -16,8 +16,8 @@ SIM_DIR = os.path.join(ROOT, "tests", "host_sim")
 SIM_LIB = os.path.join(SIM_DIR, "libstitch_sim.so")
 
 
-@pytest.fixture(scope="module")
-def sim(oracle_mod):
+def load_sim():
+    """Builds tests/host_sim/libstitch_sim.so when stale (the oracle library must exist) and returns its runner."""
     src = os.path.join(SIM_DIR, "stitch_sim.cpp")
     deps = [src, os.path.join(ROOT, "gr_lora_amd", "csrc", "lora_stitch.hpp"), os.path.join(ROOT, "gr_lora_amd", "csrc", "lora_device.h"),
             os.path.join(ROOT, "oracle", "liblora_oracle.so")]
@@ -25,26 +25,39 @@ def sim(oracle_mod):
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", "-o", SIM_LIB, src, "-L", os.path.join(ROOT, "oracle"),
                                "-llora_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle")])
     L = C.CDLL(SIM_LIB)
-    L.stitch_sim_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int,
-                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.stitch_sim_decode_streams.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_void_p]
 
-    def run(iq, sf, ctor_cr=4, demod=2, reduced=False, seg=0, slots=512, tails=True, plan=False, early=False, decoupled=False, force_rerun=0, auto=False, two_per_cu=False):
+    def run(iq, sf, ctor_cr=4, demod=2, reduced=False, seg=0, slots=512, tails=True, plan=False, early=False, decoupled=False, force_rerun=0, auto=False,
+            two_per_cu=False, streams=None):
+        """streams: [(offset, length), ...] of several streams laid back to back in iq (default: one stream, all of it); the frames' streams are
+        returned in stats["stream"], their header positions are relative to their stream"""
         a = np.ascontiguousarray(iq, dtype=np.complex64)
+        sd = np.asarray(streams if streams is not None else [(0, a.size)], dtype=np.uint64).reshape(-1, 2)
+        offs, lns = np.ascontiguousarray(sd[:, 0]), np.ascontiguousarray(sd[:, 1])
         out = np.zeros(1 << 20, dtype=np.uint8)
         lens = np.zeros(4096, dtype=np.int32)
         hp = np.zeros(4096, dtype=np.int64)
-        st = np.zeros(12, dtype=np.uint32)
+        so = np.zeros(4096, dtype=np.int32)
+        st = np.zeros(16, dtype=np.uint32)
         mode = int(tails) | (2 if plan else 0) | (4 if early else 0) | (8 if decoupled else 0) | (16 if auto else 0) | (32 if two_per_cu else 0) | ((force_rerun & 0xff) << 8)
-        n = L.stitch_sim_decode(a.ctypes.data, a.size, sf, ctor_cr, 1, int(reduced), demod, seg, slots, mode, out.ctypes.data, out.size,
-                                lens.ctypes.data, hp.ctypes.data, 4096, st.ctypes.data)
+        n = L.stitch_sim_decode_streams(a.ctypes.data, a.size, offs.ctypes.data, lns.ctypes.data, len(offs), sf, ctor_cr, 1, int(reduced), demod, seg,
+                                        slots, mode, out.ctypes.data, out.size, lens.ctypes.data, hp.ctypes.data, so.ctypes.data, 4096, st.ctypes.data)
         assert n >= 0, n
         frames, off = [], 0
         for i in range(n):
             frames.append(bytes(out[off:off + lens[i]]))
             off += int(lens[i])
         return frames, hp[:n].tolist(), dict(jobs=int(st[0]), probes=int(st[1]), slow=int(st[2]), incomplete=int(st[3]), tails=int(st[4]), planned=int(st[5]), early=int(st[6]),
-                                           payload=int(st[7]), rerun=int(st[8]), moved=int(st[9]), pending=int(st[10]))
+                                           payload=int(st[7]), rerun=int(st[8]), moved=int(st[9]), pending=int(st[10]), repairs=int(st[11]),
+                                           hash="%016x" % (int(st[12]) | int(st[13]) << 32), stream=so[:n].tolist())
     return run
+
+
+@pytest.fixture(scope="module")
+def sim(oracle_mod):
+    return load_sim()
 
 
 def _serial(O, iq, sf, ctor_cr=4, demod=2, reduced=False):
@@ -362,3 +375,136 @@ def test_decoupled_pass_one_job_per_burst(sim, oracle_mod):
     assert stats["payload"] >= 20 and 19 <= stats["jobs"] <= 128 and stats["slow"] == 0 and stats["planned"] == 1, stats
     got, gpos, stats = sim(st.iq, 7, slots=16, plan=True, early=True, auto=True)     # 20 bursts for 16 slots: not a decoupled pass
     assert got == want and gpos == wpos and stats["payload"] == 0, stats
+
+
+# ---- scheduling fingerprints: which path produced the frames, pinned against tests/golden/stitch_fingerprints.json
+# (tests/golden/make_stitch_fingerprints.py writes it).  Each workload is one an existing test above runs, with its parameters; the
+# fingerprint is the sim's FNV-1a hash over every scheduler call (jobs, payload requests, counters, publishes) plus frames, positions
+# and counters.  A refactor of the scheduler must leave all of it unchanged.
+FINGERPRINTS = os.path.join(ROOT, "tests", "golden", "stitch_fingerprints.json")
+
+
+def _ragged_sf7(seg, sigma):
+    """test_early_stopping_tail_probes_equal_serial's traffic"""
+    cfg = synth.TxConfig(sf=7, cr=4)
+    rng = np.random.default_rng(900 + seg)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(1, 48)), dtype=np.uint8)) for _ in range(30)]
+    gaps = [int(g) for g in rng.integers(0, 7 * cfg.sps, len(payloads))]
+    gaps[5] = 0; gaps[6] = 1; gaps[7] = cfg.sps // 2; gaps[8] = 2 * cfg.sps + 3
+    return synth.build_stream(payloads, cfg, gaps=gaps, rng=np.random.default_rng(seg), noise_sigma=sigma).iq
+
+
+def _noise_stale_cr(sf, cr, noise_db):
+    """test_noise_and_stale_cr_carry's traffic"""
+    cfg = synth.TxConfig(sf=sf, cr=cr)
+    rng = np.random.default_rng(77 + sf)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(4, 30)), dtype=np.uint8)) for _ in range(12)]
+    return synth.build_stream(payloads, cfg, rng=rng, noise_sigma=(10 ** (noise_db / 20.0) if noise_db else 0.0)).iq
+
+
+def _decoupled_traffic(seg, drift):
+    """test_decoupled_pass_equals_serial's traffic: clean, or noisy with a transmitter clock 40 ppm off"""
+    cfg = synth.TxConfig(sf=7, cr=4)
+    rng = np.random.default_rng(4100 + seg)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(1, 48)), dtype=np.uint8)) for _ in range(24)]
+    gaps = [int(g) for g in rng.integers(0, 9 * cfg.sps, len(payloads))]
+    gaps[3] = 0; gaps[4] = 1; gaps[9] = cfg.sps // 2
+    if not drift:
+        return synth.build_stream(payloads, cfg, gaps=gaps).iq
+    stn = synth.build_stream(payloads, cfg, gaps=gaps, rng=np.random.default_rng(5), noise_sigma=synth.awgn_sigma_for_snr(40.0, cfg))
+    t = np.arange(int(stn.iq.size / (1 + 40e-6)) - 2, dtype=np.float64) * (1 + 40e-6)
+    i0 = t.astype(np.int64)
+    fr = (t - i0).astype(np.float32)
+    return (stn.iq[i0] * (1 - fr) + stn.iq[i0 + 1] * fr).astype(np.complex64)
+
+
+def _wrong_header_branch():
+    """test_wrong_header_branch_jobs_are_rerun_in_one_batch's traffic"""
+    cfg = synth.TxConfig(sf=8, cr=1)
+    rng = np.random.default_rng(321)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(6, 24)), dtype=np.uint8)) for _ in range(40)]
+    return synth.build_stream(payloads, cfg, rng=rng, noise_sigma=10 ** (-27 / 20.0)).iq
+
+
+def _header_cr_zero(seg):
+    """test_header_with_cr_zero_ahead_of_a_cut's traffic"""
+    rng = np.random.default_rng(77 + seg)
+    pieces = []
+    for cr in (4, 0, 4, 2, 0, 0, 3, 4):
+        cfg = synth.TxConfig(sf=7, cr=cr)
+        p = bytes(rng.integers(0, 256, int(rng.integers(4, 20)), dtype=np.uint8))
+        pieces.append(synth.build_stream([p], cfg, rng=rng, tail_symbols=0.0).iq)
+    return np.concatenate(pieces + [np.zeros(4096, np.complex64)])
+
+
+def _bursts(seed):
+    """test_burst_aware_plan_equals_serial's (clean) / test_fewer_bursts_than_slots_...'s traffic"""
+    cfg = synth.TxConfig(sf=7, cr=4)
+    rng = np.random.default_rng(seed)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(4, 40)), dtype=np.uint8)) for _ in range(64)]
+    return synth.build_stream(payloads, cfg, rng=rng, gap_symbols=(2.0, 6.0)).iq
+
+
+def _truncated(before_header_symbols=-30):
+    """test_gradient_mode_and_truncated_stream's traffic, cut 30 symbols into the last packet - or, negative, this many symbols before its header
+    (inside the preamble: a probe runs out of data before it reaches a header)"""
+    cfg = synth.TxConfig(sf=7, cr=4)
+    rng = np.random.default_rng(12)
+    payloads = [bytes(rng.integers(0, 256, 20, dtype=np.uint8)) for _ in range(10)]
+    st = synth.build_stream(payloads, cfg, rng=rng)
+    return st.iq[: st.header_starts[-1] - before_header_symbols * cfg.sps]
+
+
+def _decoupled_cut_mid_packet():
+    """test_decoupled_pass_cut_mid_packet_and_other_coding_rates's first case (CR 4/5 traffic, constructor CR 4/8)"""
+    cfg = synth.TxConfig(sf=7, cr=1)
+    rng = np.random.default_rng(78)
+    payloads = [bytes(rng.integers(0, 256, int(rng.integers(4, 40)), dtype=np.uint8)) for _ in range(12)]
+    st = synth.build_stream(payloads, cfg, gaps=[int(g) for g in rng.integers(0, 6 * cfg.sps, len(payloads))])
+    return st.iq[: st.iq.size - 30 * cfg.sps]
+
+
+def fingerprint_workloads():
+    """name -> (iq, sim keyword arguments)"""
+    w = {
+        "noise_stale_cr_sf8_seg20": (_noise_stale_cr(8, 1, -32), dict(sf=8, seg=20)),
+        "noise_stale_cr_sf7_seg57_explicit_probes": (_noise_stale_cr(7, 2, -30), dict(sf=7, seg=57, tails=False)),
+        "noise_stale_cr_sf9_plan_early": (_noise_stale_cr(9, 3, None), dict(sf=9, seg=0, slots=8, plan=True, early=True)),
+        "early_probes_seg40_noisy": (_ragged_sf7(40, 10 ** (-30 / 20.0)), dict(sf=7, seg=40, slots=40, early=True)),
+        "ragged_seg16_tails": (_ragged_sf7(16, 0.0), dict(sf=7, seg=16, slots=40)),
+        "decoupled_seg40_force_rerun3": (_decoupled_traffic(40, False), dict(sf=7, seg=40, slots=40, decoupled=True, force_rerun=3)),
+        "decoupled_seg16_drift_early_force_rerun2": (_decoupled_traffic(16, True), dict(sf=7, seg=16, slots=40, early=True, decoupled=True, force_rerun=2)),
+        "wrong_header_branch": (_wrong_header_branch(), dict(sf=8, ctor_cr=4, demod=0, seg=0, slots=20, plan=True)),
+        "wrong_header_branch_early": (_wrong_header_branch(), dict(sf=8, ctor_cr=4, demod=0, seg=0, slots=20, plan=True, early=True)),
+        "burst_plan_slots16": (_bursts(4116), dict(sf=7, seg=0, slots=16, plan=True)),
+        "header_cr_zero_seg33": (_header_cr_zero(33), dict(sf=7, ctor_cr=4, seg=33, slots=64)),
+        "two_per_cu_auto_slots100": (_bursts(5200), dict(sf=7, seg=0, slots=100, plan=True, auto=True, two_per_cu=True)),
+        "cut_mid_packet_grad_seg33": (_truncated(), dict(sf=7, demod=0, seg=33)),
+        "cut_mid_packet_decoupled_seg24": (_decoupled_cut_mid_packet(), dict(sf=7, ctor_cr=4, seg=24, slots=24, decoupled=True)),
+        "cut_mid_preamble_seg20": (_truncated(4), dict(sf=7, seg=20)),
+    }
+    parts = [_ragged_sf7(23, 10 ** (-30 / 20.0)), _noise_stale_cr(7, 2, -30), _truncated(), _decoupled_traffic(40, False)]
+    offs = np.cumsum([0] + [p.size for p in parts[:-1]]).tolist()
+    w["multi_stream_4_seg20"] = (np.concatenate(parts), dict(sf=7, seg=20, slots=40, streams=[(o, p.size) for o, p in zip(offs, parts)]))
+    return w
+
+
+def fingerprints(sim):
+    out = {}
+    for name, (iq, kw) in fingerprint_workloads().items():
+        kw = dict(kw)
+        frames, pos, stats = sim(iq, kw.pop("sf"), **kw)
+        out[name] = dict(frames=[f.hex() for f in frames], header_pos=pos, stats=stats)
+    return out
+
+
+def test_scheduling_fingerprints_match_golden(sim):
+    """Frames, header positions, counters (repairs included) and the hash over every scheduler call, per workload, equal the golden's: a change
+    of the scheduler that keeps the frames but takes other paths (a repair turned into a serial walk) shows here."""
+    import json
+    with open(FINGERPRINTS) as f:
+        want = json.load(f)
+    got = fingerprints(sim)
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name
