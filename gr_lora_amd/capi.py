@@ -38,6 +38,18 @@ EXPORTS_CHANNELIZER = [
 ]
 
 
+EXPORTS_FILTERBANK = [
+    "lora_hip_filterbank_create", "lora_hip_filterbank_destroy", "lora_hip_filterbank_last_error", "lora_hip_filterbank_taps",
+    "lora_hip_filterbank_output_items", "lora_hip_filterbank_run_device", "lora_hip_filterbank_work", "lora_hip_filterbank_last_kernel_ms",
+]
+
+
+class FilterBankConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("samp_rate", C.c_double), ("grid_offset_hz", C.c_double), ("n_grid", C.c_uint32),
+                ("channels", C.POINTER(C.c_int32)), ("n_channels", C.c_uint32), ("bandwidth", C.c_uint32), ("decimation", C.c_uint32),
+                ("device", C.c_int32), ("cutoff_hz", C.c_float), ("transition_hz", C.c_float), ("flags", C.c_uint32)]
+
+
 class ChannelizerConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("samp_rate", C.c_float), ("center_freq", C.c_float), ("channel_list", C.POINTER(C.c_float)),
                 ("n_channels", C.c_uint32), ("bandwidth", C.c_uint32), ("decimation", C.c_uint32), ("device", C.c_int32),
@@ -191,6 +203,18 @@ def load():
     L.lora_hip_channelizer_apply_cfo.argtypes = [vp, C.c_float]
     L.lora_hip_channelizer_last_kernel_ms.argtypes = [vp]
     L.lora_hip_channelizer_last_kernel_ms.restype = C.c_float
+    L.lora_hip_filterbank_create.argtypes = [C.POINTER(FilterBankConfig), C.POINTER(vp)]
+    L.lora_hip_filterbank_destroy.argtypes = [vp]
+    L.lora_hip_filterbank_destroy.restype = None
+    L.lora_hip_filterbank_last_error.argtypes = [vp]
+    L.lora_hip_filterbank_last_error.restype = C.c_char_p
+    L.lora_hip_filterbank_taps.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lora_hip_filterbank_output_items.argtypes = [vp, C.c_size_t]
+    L.lora_hip_filterbank_output_items.restype = C.c_size_t
+    L.lora_hip_filterbank_run_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.lora_hip_filterbank_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lora_hip_filterbank_last_kernel_ms.argtypes = [vp]
+    L.lora_hip_filterbank_last_kernel_ms.restype = C.c_float
     _lib = L
     return L
 
@@ -560,6 +584,66 @@ class Channelizer:
     def close(self):
         if self.h:
             self.L.lora_hip_channelizer_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FilterBank:
+    """lora_hip_filterbank_* (include/lora_hip_filterbank.h): the polyphase DFT channeliser for channels on a uniform grid.
+    Row c is the channeliser's output at grid_offset + channels[c] * samp_rate / n_grid (Hz from the capture's centre)."""
+
+    def __init__(self, samp_rate, grid_offset, n_grid, channels, bandwidth, decimation=1, device=0, cutoff_hz=0.0, transition_hz=0.0, flags=0):
+        self.L = load()
+        self.channels = [int(k) for k in channels]
+        self.n_channels = len(self.channels)
+        self._chan = (C.c_int32 * max(self.n_channels, 1))(*self.channels)
+        cfg = FilterBankConfig(struct_size=C.sizeof(FilterBankConfig), samp_rate=float(samp_rate), grid_offset_hz=float(grid_offset), n_grid=int(n_grid),
+                               channels=self._chan, n_channels=self.n_channels, bandwidth=int(bandwidth), decimation=int(decimation), device=int(device),
+                               cutoff_hz=float(cutoff_hz), transition_hz=float(transition_hz), flags=int(flags))
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_filterbank_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            raise LoraHipError(st, self.L.lora_hip_strerror(st).decode())
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, (self.L.lora_hip_filterbank_last_error(self.h) or b"").decode() or self.L.lora_hip_strerror(st).decode())
+
+    def taps(self) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_filterbank_taps(self.h, None, 0, C.byref(n)))
+        t = np.zeros(n.value, dtype=np.float32)
+        self._check(self.L.lora_hip_filterbank_taps(self.h, t.ctypes.data, t.size, C.byref(n)))
+        return t
+
+    def output_items(self, n_in: int) -> int:
+        return int(self.L.lora_hip_filterbank_output_items(self.h, n_in))
+
+    def work(self, x) -> np.ndarray:
+        """Host buffers in and out: complex64[n_in] -> complex64[n_channels, n_out]."""
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        no = self.output_items(a.size)
+        out = np.zeros((self.n_channels, max(no, 1)), dtype=np.complex64)
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_filterbank_work(self.h, a.ctypes.data, a.size, out.ctypes.data, out.shape[1], C.byref(n)))
+        return out[:, : n.value]
+
+    def run_device(self, d_in: int, n_in: int, d_out: int, out_stride: int, stream: int = 0) -> int:
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_filterbank_run_device(self.h, d_in, n_in, d_out, out_stride, C.byref(n), stream))
+        return int(n.value)
+
+    def kernel_ms(self) -> float:
+        return float(self.L.lora_hip_filterbank_last_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.lora_hip_filterbank_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -6,6 +6,8 @@ Same names, argument order and meaning as the reference module `lora`:
   lora.lora_receiver(samp_rate, center_freq, channel_list, bandwidth, sf, implicit, cr, crc,
                      reduced_rate=False, conj=False, decimation=1, disable_channelization=False,
                      disable_drift_correction=False)            (python/lora_receiver.py:30)
+  lora.gateway_receiver(samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sf, implicit, cr, crc,
+                        decimation)                  (not upstream: every channel of a uniform grid, one filter bank + one mux)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -230,6 +232,85 @@ class channelizer:
         self._h.close()
         self.center_freq = float(center_freq)
         self._h = capi.Channelizer(self.fs, self.center_freq, self.channel_list[:1], self.bandwidth, self.decimation, self.device)
+
+
+class filterbank_channelizer:
+    """Like `channelizer`, for channels on a uniform grid, and every selected row is output: row c is the channeliser's output
+    at center_freq + grid_offset + channels[c] * samp_rate / n_grid, computed by the polyphase DFT filter bank
+    (include/lora_hip_filterbank.h) in one launch for all of them.  No host fall-back."""
+
+    def __init__(self, samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, decimation=1, device=0):
+        self.fs = float(samp_rate)
+        self.center_freq = float(center_freq)
+        self.grid_offset = float(grid_offset)
+        self.n_grid = int(n_grid)
+        self.channels = [int(k) for k in channels]
+        self.bandwidth = int(bandwidth)
+        self.decimation = int(decimation)
+        self.device = device
+        self._h = capi.FilterBank(samp_rate, grid_offset, n_grid, self.channels, bandwidth, decimation, device)
+        self.taps = self._h.taps()
+
+    def channel_freq(self, kappa) -> float:
+        """Absolute centre frequency (Hz) of grid index kappa."""
+        return self.center_freq + self.grid_offset + int(kappa) * self.fs / self.n_grid
+
+    def work(self, x) -> np.ndarray:
+        """complex64[n_in] -> complex64[len(channels), n_out]."""
+        x = np.asarray(x, dtype=np.complex64)
+        return self._h.work(x)
+
+    def close(self):
+        self._h.close()
+
+
+class gateway_receiver(_MsgBlock):
+    """A gateway's receiver: one wide-band capture -> filterbank_channelizer (every grid channel of the band plan in one launch)
+    -> one capi.Mux with a decoder per channel.  Each frame is published unchanged on "frames" and as (grid_index, blob) on
+    "channel_frames"; per channel the frames are what lora_receiver on that channel alone publishes from the same channel samples."""
+
+    def __init__(self, samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sf, implicit, cr, crc, decimation=1,
+                 reduced_rate=False, disable_drift_correction=False, device=0, demod=capi.DEMOD_FFT_COMPAT, batch_items=0, latency_ms=None):
+        super().__init__()
+        self.samp_rate = samp_rate
+        self.center_freq = center_freq
+        self.channels = [int(k) for k in channels]
+        self.sf = sf
+        self.decimation = int(decimation)
+        if sf < 6 or sf > 12:  # as decoder (decoder_impl.cc:57-61)
+            sys.stderr.write("[LoRa Decoder] ERROR : Spreading factor should be between 6 and 12 (inclusive)!\n"
+                             "                       Other values are currently not supported.\n")
+            raise SystemExit(1)
+        self.filterbank = filterbank_channelizer(samp_rate, center_freq, grid_offset, n_grid, self.channels, bandwidth, decimation, device)
+        self.mux = capi.Mux(len(self.channels), samp_rate=samp_rate / self.decimation, bandwidth=bandwidth, sf=sf, implicit=implicit, cr=cr,
+                            crc=crc, reduced_rate=reduced_rate, disable_drift_correction=disable_drift_correction, device=device, demod=demod,
+                            batch_items=batch_items)
+        if latency_ms is not None:
+            self.mux.set_latency(float(latency_ms))
+        self.message_port_register_out("frames")
+        self.message_port_register_out("channel_frames")
+
+    def work(self, input_items) -> int:
+        x = np.asarray(input_items, dtype=np.complex64)
+        rows = self.filterbank.work(x)
+        for c in range(len(self.channels)):
+            if rows.shape[1]:
+                self.mux.work(c, rows[c])
+        self._publish()
+        return x.size
+
+    def stop(self):
+        self.mux.flush()
+        self._publish()
+
+    def _publish(self):
+        for blob, info in self.mux.drain():
+            self.message_port_pub("frames", blob)
+            self.message_port_pub("channel_frames", (self.channels[info.stream], blob))
+
+    def close(self):
+        self.mux.close()
+        self.filterbank.close()
 
 
 class lora_receiver(_MsgBlock):
