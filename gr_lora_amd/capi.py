@@ -40,8 +40,19 @@ EXPORTS_CHANNELIZER = [
 
 EXPORTS_FILTERBANK = [
     "lora_hip_filterbank_create", "lora_hip_filterbank_destroy", "lora_hip_filterbank_last_error", "lora_hip_filterbank_taps",
-    "lora_hip_filterbank_output_items", "lora_hip_filterbank_run_device", "lora_hip_filterbank_work", "lora_hip_filterbank_last_kernel_ms",
+    "lora_hip_filterbank_output_items", "lora_hip_filterbank_run_device", "lora_hip_filterbank_run_device_rows", "lora_hip_filterbank_work",
+    "lora_hip_filterbank_last_kernel_ms",
 ]
+
+
+EXPORTS_GATEWAY = [
+    "lora_hip_gateway_create", "lora_hip_gateway_destroy", "lora_hip_gateway_last_error", "lora_hip_gateway_work", "lora_hip_gateway_work_device",
+    "lora_hip_gateway_flush", "lora_hip_gateway_set_latency", "lora_hip_gateway_frames_available", "lora_hip_gateway_poll_frame", "lora_hip_gateway_stats",
+]
+
+FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
+GATEWAY_MAX_DECODERS = 7      # include/lora_hip_gateway.h
+GATEWAY_STEP_OUTPUTS = 65536  # include/lora_hip_gateway.h
 
 
 class FilterBankConfig(C.Structure):
@@ -100,6 +111,22 @@ class WindowStats(C.Structure):
 class Preamble(C.Structure):
     _fields_ = [("header_pos", C.c_int64), ("run_pos", C.c_int64), ("stream", C.c_uint32), ("run_len", C.c_uint32), ("bin", C.c_int32), ("sfd_index", C.c_int32),
                 ("pmr", C.c_float), ("cfo_bins", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int32)]
+
+
+class GatewayConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("filterbank", FilterBankConfig), ("decoders", C.POINTER(Config)), ("n_decoders", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class GatewayFrameInfo(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("grid_index", C.c_int32), ("sf", C.c_uint32), ("decoder", C.c_uint32), ("length", C.c_uint32),
+                ("reserved", C.c_uint32), ("header_pos", C.c_int64), ("end_pos", C.c_int64)]
+
+
+class GatewayStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_decoders", C.c_uint32), ("passes", C.c_uint64 * GATEWAY_MAX_DECODERS),
+                ("passes_by_latency", C.c_uint64 * GATEWAY_MAX_DECODERS), ("filterbank_calls", C.c_uint64), ("filterbank_ms", C.c_double),
+                ("items_in", C.c_uint64), ("step_outputs", C.c_uint64)]
 
 
 class LoraHipError(RuntimeError):
@@ -215,6 +242,20 @@ def load():
     L.lora_hip_filterbank_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lora_hip_filterbank_last_kernel_ms.argtypes = [vp]
     L.lora_hip_filterbank_last_kernel_ms.restype = C.c_float
+    L.lora_hip_filterbank_run_device_rows.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.lora_hip_gateway_create.argtypes = [C.POINTER(GatewayConfig), C.POINTER(vp)]
+    L.lora_hip_gateway_destroy.argtypes = [vp]
+    L.lora_hip_gateway_destroy.restype = None
+    L.lora_hip_gateway_last_error.argtypes = [vp]
+    L.lora_hip_gateway_last_error.restype = C.c_char_p
+    L.lora_hip_gateway_work.argtypes = [vp, vp, C.c_size_t]
+    L.lora_hip_gateway_work_device.argtypes = [vp, vp, C.c_size_t, vp]
+    L.lora_hip_gateway_flush.argtypes = [vp]
+    L.lora_hip_gateway_set_latency.argtypes = [vp, C.c_float]
+    L.lora_hip_gateway_frames_available.argtypes = [vp]
+    L.lora_hip_gateway_frames_available.restype = C.c_size_t
+    L.lora_hip_gateway_poll_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(GatewayFrameInfo)]
+    L.lora_hip_gateway_stats.argtypes = [vp, C.POINTER(GatewayStats)]
     _lib = L
     return L
 
@@ -638,6 +679,13 @@ class FilterBank:
         self._check(self.L.lora_hip_filterbank_run_device(self.h, d_in, n_in, d_out, out_stride, C.byref(n), stream))
         return int(n.value)
 
+    def run_device_rows(self, d_in: int, n_in: int, row_ptrs: Sequence[int], n_dst: int, max_out: int, stream: int = 0) -> int:
+        """row_ptrs[dst * n_channels + c]: device address of row c's first new item for destination dst."""
+        ptrs = (C.c_void_p * max(len(row_ptrs), 1))(*[int(p) for p in row_ptrs])
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_filterbank_run_device_rows(self.h, d_in, n_in, ptrs, int(n_dst), int(max_out), C.byref(n), stream))
+        return int(n.value)
+
     def kernel_ms(self) -> float:
         return float(self.L.lora_hip_filterbank_last_kernel_ms(self.h))
 
@@ -651,3 +699,77 @@ class FilterBank:
             self.close()
         except Exception:
             pass
+
+
+class Gateway:
+    """lora_hip_gateway_* (include/lora_hip_gateway.h): one filter bank over a wide-band capture, one decoder per spreading factor
+    on every row, fed on the device.  decoders: one dict of Config fields per spreading factor (sf, cr, crc, implicit,
+    reduced_rate, demod, ...); samp_rate, bandwidth and device follow the filter bank."""
+
+    def __init__(self, samp_rate, grid_offset, n_grid, channels, bandwidth, decoders, decimation=1, device=0, cutoff_hz=0.0, transition_hz=0.0, flags=0):
+        self.L = load()
+        self.channels = [int(k) for k in channels]
+        self._chan = (C.c_int32 * max(len(self.channels), 1))(*self.channels)
+        fb = FilterBankConfig(struct_size=C.sizeof(FilterBankConfig), samp_rate=float(samp_rate), grid_offset_hz=float(grid_offset), n_grid=int(n_grid),
+                              channels=self._chan, n_channels=len(self.channels), bandwidth=int(bandwidth), decimation=int(decimation), device=int(device),
+                              cutoff_hz=float(cutoff_hz), transition_hz=float(transition_hz), flags=0)
+        rate = float(np.float32(float(samp_rate) / int(decimation)))
+        self.sfs = [int(d["sf"]) for d in decoders]
+        self._dec = (Config * max(len(decoders), 1))()
+        for i, d in enumerate(decoders):
+            kw = dict(samp_rate=rate, bandwidth=int(bandwidth), device=int(device), cr=4, crc=1, demod=DEMOD_FFT_COMPAT)
+            kw.update(d)
+            for k in ("implicit", "crc", "reduced_rate", "disable_drift_correction"):
+                if k in kw:
+                    kw[k] = int(bool(kw[k]))
+            self._dec[i] = Config(struct_size=C.sizeof(Config), **kw)
+        cfg = GatewayConfig(struct_size=C.sizeof(GatewayConfig), filterbank=fb, decoders=self._dec, n_decoders=len(decoders), flags=int(flags))
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_gateway_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            raise LoraHipError(st, "%s (%s)" % (self.L.lora_hip_strerror(st).decode(), self.L.lora_hip_last_error(None).decode()))
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, "%s (%s)" % (self.L.lora_hip_strerror(st).decode(), (self.L.lora_hip_gateway_last_error(self.h) or b"").decode()))
+
+    def work(self, iq: np.ndarray):
+        """complex64 wide-band items from host memory."""
+        a = np.ascontiguousarray(iq, dtype=np.complex64)
+        self._check(self.L.lora_hip_gateway_work(self.h, a.ctypes.data, a.size))
+
+    def work_device(self, ptr: int, n: int, stream: int = 0):
+        """n complex64 items at device address ptr, read after the work queued on stream."""
+        self._check(self.L.lora_hip_gateway_work_device(self.h, ptr, int(n), stream))
+
+    def flush(self):
+        self._check(self.L.lora_hip_gateway_flush(self.h))
+
+    def set_latency(self, ms: float):
+        self._check(self.L.lora_hip_gateway_set_latency(self.h, float(ms)))
+
+    def drain(self) -> List[Tuple[bytes, GatewayFrameInfo]]:
+        out = []
+        buf = (C.c_uint8 * 320)()
+        while self.L.lora_hip_gateway_frames_available(self.h):
+            n = C.c_size_t(0)
+            info = GatewayFrameInfo()
+            self._check(self.L.lora_hip_gateway_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info)))
+            out.append((bytes(buf[: n.value]), info))
+        return out
+
+    def stats(self) -> dict:
+        s = GatewayStats(struct_size=C.sizeof(GatewayStats))
+        self._check(self.L.lora_hip_gateway_stats(self.h, C.byref(s)))
+        nd = s.n_decoders
+        return {"passes": {self.sfs[i]: int(s.passes[i]) for i in range(nd)},
+                "passes_by_latency": {self.sfs[i]: int(s.passes_by_latency[i]) for i in range(nd)},
+                "filterbank_calls": int(s.filterbank_calls), "filterbank_ms": float(s.filterbank_ms), "items_in": int(s.items_in),
+                "step_outputs": int(s.step_outputs)}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lora_hip_gateway_destroy(self.h)
+            self.h = None
+
+    __del__ = close

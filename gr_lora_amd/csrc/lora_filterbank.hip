@@ -82,10 +82,17 @@ struct PfbArgs {
     int xs_slots;          // LDS slots of the staged span
 };
 
+static_assert(LORA_HIP_FILTERBANK_MAX_DST * kCB <= 64, "run_device_rows: one lane per (destination, row of a channel group)");
+typedef __attribute__((address_space(1))) unsigned long long pfb_gu64; // (global stores for run_device_rows' destinations)
+
 __device__ __host__ __forceinline__ int pfb_slot(int i) { return i + (i >> 4); }
 
 __device__ __forceinline__ float2 pfb_cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 
+// kRows = false (run_device): row r at A.out + r A.out_stride.  kRows = true (run_device_rows): A.out is a device table of
+// n_dst * n_sel row base pointers (float2 *) and A.out_stride is n_dst; each output goes to rows[d n_sel + r] for every d,
+// the same value from the same registers.
+template <bool kRows>
 __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs A, const float *__restrict__ taps, const float2 *__restrict__ tw)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -117,6 +124,7 @@ __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs A, const float *_
     const int lane = threadIdx.x & 63;
     const bool act = lane < cw;
     const int n_cg = A.cpad / kCB;
+    const int n_dst = kRows ? (int)A.out_stride : 0;
     __syncthreads();
     for (int k0 = 0; k0 < A.nc; k0 += A.g) {
         // branch phase: tasks (r, gi) over the waves
@@ -150,6 +158,11 @@ __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs A, const float *_
         // DFT phase: tasks (channel group, gi) over the waves
         for (int task = wave; task < n_cg * A.g; task += kWaves) {
             const int cg = task % n_cg, gi = task / n_cg;
+            unsigned long long mine = 0; // rows mode: lane l holds row cg kCB + (l % kCB) of destination l / kCB (read back per store)
+            if constexpr (kRows) {
+                const int rd = lane / kCB, rc = cg * kCB + lane % kCB;
+                if (rd < n_dst && rc < A.n_sel) mine = reinterpret_cast<const unsigned long long *>(A.out)[(size_t)rd * A.n_sel + rc];
+            }
             if (act) {
                 float2 acc[kCB];
 #pragma unroll
@@ -170,7 +183,18 @@ __global__ __launch_bounds__(kThreads) void pfb_kernel(PfbArgs A, const float *_
 #pragma unroll
                     for (int c = 0; c < kCB; c++) {
                         const int row = cg * kCB + c;
-                        if (row < A.n_sel) A.out[(size_t)row * A.out_stride + m] = pfb_cmul(acc[c], base);
+                        if (row < A.n_sel) {
+                            if constexpr (kRows) {
+                                const float2 y = pfb_cmul(acc[c], base);
+                                for (int d = 0; d < n_dst; d++) {
+                                    const unsigned long long p = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)mine, d * kCB + c) |
+                                                                 (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), d * kCB + c) << 32;
+                                    reinterpret_cast<pfb_gu64 *>(p)[m] = __builtin_bit_cast(unsigned long long, y);
+                                }
+                            } else {
+                                A.out[(size_t)row * A.out_stride + m] = pfb_cmul(acc[c], base);
+                            }
+                        }
                     }
                 }
             }
@@ -197,7 +221,9 @@ struct lora_hip_filterbank {
     int device = 0;
     long long n_abs = 0;           // input items consumed so far
     float *d_taps = nullptr;
-    float2 *d_tw = nullptr, *d_hist = nullptr, *d_stage_in = nullptr, *d_stage_out = nullptr;
+    float2 *d_tw = nullptr, *d_hist = nullptr, *d_hist2 = nullptr, *d_stage_in = nullptr, *d_stage_out = nullptr;
+    float2 **d_rows = nullptr;     // run_device_rows' pointer table (LORA_HIP_FILTERBANK_MAX_DST * n_channels entries)
+    std::vector<float2 *> rows;    // ... and its host copy (alive until the upload is done)
     size_t stage_in_cap = 0, stage_out_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.0f;
@@ -299,12 +325,15 @@ lora_hip_status lora_hip_filterbank_create(const lora_hip_filterbank_config_t *c
         if (hipMalloc((void **)&h->d_taps, (size_t)L * sizeof(float)) != hipSuccess ||
             hipMalloc((void **)&h->d_tw, tw.size() * sizeof(float2)) != hipSuccess ||
             hipMalloc((void **)&h->d_hist, std::max<size_t>(nh, 1) * sizeof(float2)) != hipSuccess ||
+            hipMalloc((void **)&h->d_hist2, std::max<size_t>(nh, 1) * sizeof(float2)) != hipSuccess ||
+            hipMalloc((void **)&h->d_rows, (size_t)LORA_HIP_FILTERBANK_MAX_DST * nsel * sizeof(float2 *)) != hipSuccess ||
             hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { st = LORA_HIP_ERR_NOMEM; break; }
         if (hipMemcpy(h->d_taps, padded.data(), (size_t)L * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(h->d_hist, 0, std::max<size_t>(nh, 1) * sizeof(float2)) != hipSuccess) { st = LORA_HIP_ERR_HIP; break; }
         // one attribute for the one kernel, whatever the handle: the largest tile any handle may plan
-        if (hipFuncSetAttribute((const void *)pfb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) { st = LORA_HIP_ERR_HIP; break; }
+        if (hipFuncSetAttribute((const void *)pfb_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess ||
+            hipFuncSetAttribute((const void *)pfb_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax) != hipSuccess) { st = LORA_HIP_ERR_HIP; break; }
     } while (false);
     if (st != LORA_HIP_OK) { lora_hip_filterbank_destroy(h); return st; }
     *out = h;
@@ -318,6 +347,8 @@ void lora_hip_filterbank_destroy(lora_hip_filterbank_t *h)
     if (h->d_taps) (void)hipFree(h->d_taps);
     if (h->d_tw) (void)hipFree(h->d_tw);
     if (h->d_hist) (void)hipFree(h->d_hist);
+    if (h->d_hist2) (void)hipFree(h->d_hist2);
+    if (h->d_rows) (void)hipFree(h->d_rows);
     if (h->d_stage_in) (void)hipFree(h->d_stage_in);
     if (h->d_stage_out) (void)hipFree(h->d_stage_out);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -369,7 +400,7 @@ lora_hip_status lora_hip_filterbank_run_device(lora_hip_filterbank_t *h, const v
         const long long T = (long long)h->cw * h->nc;
         const unsigned tiles = (unsigned)(((long long)no + T - 1) / T);
         FB_TRY(h, hipEventRecord(h->ev0, st));
-        hipLaunchKernelGGL(pfb_kernel, dim3(tiles), dim3(kThreads), h->lds, st, a, (const float *)h->d_taps, (const float2 *)h->d_tw);
+        hipLaunchKernelGGL(pfb_kernel<false>, dim3(tiles), dim3(kThreads), h->lds, st, a, (const float *)h->d_taps, (const float2 *)h->d_tw);
         FB_TRY(h, hipGetLastError());
         FB_TRY(h, hipEventRecord(h->ev1, st));
     }
@@ -384,6 +415,57 @@ lora_hip_status lora_hip_filterbank_run_device(lora_hip_filterbank_t *h, const v
             FB_TRY(h, hipMemcpy(tmp.data(), h->d_hist + n_in, keep * sizeof(float2), hipMemcpyDeviceToHost));
             FB_TRY(h, hipMemcpy(tmp.data() + keep, d_in, n_in * sizeof(float2), hipMemcpyDeviceToHost));
             FB_TRY(h, hipMemcpy(h->d_hist, tmp.data(), tmp.size() * sizeof(float2), hipMemcpyHostToDevice));
+        }
+    }
+    FB_TRY(h, hipStreamSynchronize(st));
+    if (no) FB_TRY(h, hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+    h->n_abs += (long long)n_in;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_filterbank_run_device_rows(lora_hip_filterbank_t *h, const void *d_in, size_t n_in, void *const *row_ptrs, uint32_t n_dst,
+                                                    size_t max_out, size_t *n_out, void *hip_stream)
+{
+    if (!h || !n_out || (n_in && (!d_in || !row_ptrs)) || n_dst < 1 || n_dst > LORA_HIP_FILTERBANK_MAX_DST) return LORA_HIP_ERR_ARG;
+    const size_t nsel = h->channels.size();
+    if (n_in)
+        for (size_t i = 0; i < (size_t)n_dst * nsel; i++)
+            if (!row_ptrs[i] || ((uintptr_t)row_ptrs[i] & 7u)) return ffail(h, LORA_HIP_ERR_ARG, "row pointer %zu is NULL or not 8-byte aligned", i);
+    const size_t no = lora_hip_filterbank_output_items(h, n_in);
+    *n_out = no;
+    if (no > max_out) return ffail(h, LORA_HIP_ERR_OVERFLOW, "max_out %zu < %zu output items", max_out, no);
+    hipStream_t st = (hipStream_t)hip_stream;
+    FB_TRY(h, hipSetDevice(h->device));
+    const int nh = (int)h->taps.size() - 1;
+    const long long D = h->D, M = h->M;
+    h->last_ms = 0.0f;
+    if (no) {
+        h->rows.assign((float2 *const *)row_ptrs, (float2 *const *)row_ptrs + (size_t)n_dst * nsel);
+        FB_TRY(h, hipMemcpyAsync(h->d_rows, h->rows.data(), h->rows.size() * sizeof(float2 *), hipMemcpyHostToDevice, st));
+        PfbArgs a{};
+        a.in = (const float2 *)d_in; a.hist = h->d_hist; a.out = (float2 *)h->d_rows;
+        a.tps = h->cfg.grid_offset_hz / h->cfg.samp_rate;
+        a.n_abs = h->n_abs; a.n_in = (long long)n_in; a.first = (D - (h->n_abs % D)) % D; a.n_out = (long long)no;
+        a.out_stride = (long long)n_dst;
+        a.M = h->M; a.Q = h->Q; a.D = h->D; a.nhist = nh; a.n_sel = (int)nsel; a.cpad = h->cpad;
+        a.base_mod = (int)((h->n_abs + a.first) % M);
+        a.cw = h->cw; a.g = h->g; a.nc = h->nc; a.xs_slots = h->xs_slots;
+        const long long T = (long long)h->cw * h->nc;
+        const unsigned tiles = (unsigned)(((long long)no + T - 1) / T);
+        FB_TRY(h, hipEventRecord(h->ev0, st));
+        hipLaunchKernelGGL(pfb_kernel<true>, dim3(tiles), dim3(kThreads), h->lds, st, a, (const float *)h->d_taps, (const float2 *)h->d_tw);
+        FB_TRY(h, hipGetLastError());
+        FB_TRY(h, hipEventRecord(h->ev1, st));
+    }
+    // the next call's history, on the device whatever n_in: the last nh items of (history, input)
+    if (nh > 0 && n_in) {
+        if (n_in >= (size_t)nh) {
+            FB_TRY(h, hipMemcpyAsync(h->d_hist, (const float2 *)d_in + (n_in - (size_t)nh), (size_t)nh * sizeof(float2), hipMemcpyDeviceToDevice, st));
+        } else {
+            const size_t keep = (size_t)nh - n_in;
+            FB_TRY(h, hipMemcpyAsync(h->d_hist2, h->d_hist + n_in, keep * sizeof(float2), hipMemcpyDeviceToDevice, st));
+            FB_TRY(h, hipMemcpyAsync(h->d_hist2 + keep, d_in, n_in * sizeof(float2), hipMemcpyDeviceToDevice, st));
+            std::swap(h->d_hist, h->d_hist2);
         }
     }
     FB_TRY(h, hipStreamSynchronize(st));

@@ -22,6 +22,7 @@
 #include "../../include/lora_hip.h"
 #include "lora_device.h"
 #include "lora_stitch.hpp"
+#include "lora_mux_dev.h"
 
 using namespace lora_hip;
 
@@ -1436,6 +1437,7 @@ struct lora_hip_mux {
     std::vector<Chan> ch;
     hipStream_t copy_st = nullptr, comp_st = nullptr;
     hipEvent_t up_ev = nullptr, tail_ev = nullptr;
+    hipEvent_t fed_ev = nullptr;     // the device-fed path (lora_mux_dev.h): recorded on copy_st for a writer of the chunk area to wait on
     bool inflight = false;
     float max_latency_ms = 50.0f;
     size_t max_ahead = 0;            // surplus of one channel (items in host memory) at which a pass goes without waiting for the others
@@ -1485,6 +1487,7 @@ void lora_hip_mux_destroy(lora_hip_mux_t *m)
     for (int i = 0; i < 2; i++) m->dbuf[i].release();
     if (m->up_ev) (void)hipEventDestroy(m->up_ev);
     if (m->tail_ev) (void)hipEventDestroy(m->tail_ev);
+    if (m->fed_ev) (void)hipEventDestroy(m->fed_ev);
     if (m->copy_st) (void)hipStreamDestroy(m->copy_st);
     if (m->comp_st) (void)hipStreamDestroy(m->comp_st);
     if (m->h) { m->h->pass_open = false; lora_hip_destroy(m->h); }
@@ -1550,6 +1553,8 @@ static lora_hip_status mux_upload(lora_hip_mux *m, uint32_t c, const float2 *src
     C.fill += n;
     return LORA_HIP_OK;
 }
+
+static lora_hip_status mux_pass_loop(lora_hip_mux *m);
 
 // launches a pass over what every channel holds (collecting the pass before it), then refills the new chunk from the surplus
 static lora_hip_status mux_rotate(lora_hip_mux *m, bool by_latency)
@@ -1647,6 +1652,14 @@ lora_hip_status lora_hip_mux_work(lora_hip_mux_t *m, uint32_t channel, const flo
     }
     if (left) C.ahead.insert(C.ahead.end(), src, src + left); // this channel is a chunk ahead of the slowest one
     MUX_TRY(m, hipStreamSynchronize(m->copy_st)); // the caller may reuse its buffer
+    return mux_pass_loop(m);
+}
+
+// after new samples: a pass while every chunk is full, and the latency bound (lora_hip_mux_work and the device-fed path)
+static lora_hip_status mux_pass_loop(lora_hip_mux *m)
+{
+    lora_hip_decoder *h = m->h;
+    lora_hip_status s;
     for (;;) { // a pass when every channel's chunk is full (again, while the surplus refills whole chunks) - or when one channel's surplus
                // has reached max_ahead (a silent or stalled neighbour must not let it grow without bound when the latency bound is off:
                // the others then go into the pass with what they hold)
@@ -1666,6 +1679,56 @@ lora_hip_status lora_hip_mux_work(lora_hip_mux_t *m, uint32_t channel, const flo
     }
     return LORA_HIP_OK;
 }
+
+} // extern "C"
+
+namespace lora_mux_dev {
+
+lora_hip_status collect_if_done(lora_hip_mux *m)
+{
+    m->err.clear();
+    lora_hip_status s = LORA_HIP_OK;
+    if (m->inflight && m->h->pending.open && hipEventQuery(m->h->ev_done) == hipSuccess) s = mux_collect(m);
+    (void)hipGetLastError();
+    return s;
+}
+
+size_t batch(const lora_hip_mux *m) { return m->batch; }
+
+size_t room(const lora_hip_mux *m)
+{
+    size_t r = m->batch;
+    for (const auto &c : m->ch) r = std::min(r, m->batch - c.fill);
+    return r;
+}
+
+void rows(const lora_hip_mux *m, void **out)
+{
+    for (uint32_t c = 0; c < m->n; c++) out[c] = m->dbuf[m->cur].p + (size_t)c * m->region + m->tailcap + m->ch[c].fill;
+}
+
+lora_hip_status before_write(lora_hip_mux *m, hipStream_t st)
+{
+    // copy_st holds the moves of channels too short for a pass (they read the chunk area of what becomes the current buffer
+    // one rotation later) and already waits for the tail copies of the last collect (tail_ev, same reason): st waits for both
+    if (!m->fed_ev) MUX_TRY(m, hipEventCreateWithFlags(&m->fed_ev, hipEventDisableTiming));
+    MUX_TRY(m, hipEventRecord(m->fed_ev, m->copy_st));
+    MUX_TRY(m, hipStreamWaitEvent(st, m->fed_ev, 0));
+    return LORA_HIP_OK;
+}
+
+lora_hip_status commit(lora_hip_mux *m, size_t n, hipEvent_t written)
+{
+    if (n > room(m)) { m->err = "device-fed commit beyond the chunk"; return LORA_HIP_ERR_INTERNAL; }
+    MUX_TRY(m, hipStreamWaitEvent(m->copy_st, written, 0)); // the next pass waits for copy_st (up_ev), hence for the writer
+    for (auto &c : m->ch) c.fill += n;
+    if (n && !m->have_first) { m->have_first = true; m->t_first = std::chrono::steady_clock::now(); }
+    return mux_pass_loop(m);
+}
+
+} // namespace lora_mux_dev
+
+extern "C" {
 
 lora_hip_status lora_hip_mux_flush(lora_hip_mux_t *m)
 {

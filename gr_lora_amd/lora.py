@@ -8,6 +8,9 @@ Same names, argument order and meaning as the reference module `lora`:
                      disable_drift_correction=False)            (python/lora_receiver.py:30)
   lora.gateway_receiver(samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sf, implicit, cr, crc,
                         decimation)                  (not upstream: every channel of a uniform grid, one filter bank + one mux)
+  lora.multi_sf_gateway_receiver(samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sfs, ...)
+                                              (not upstream: every channel x every SF, one filter bank feeding one mux per SF
+                                              on the device)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -311,6 +314,89 @@ class gateway_receiver(_MsgBlock):
     def close(self):
         self.mux.close()
         self.filterbank.close()
+
+
+def lorawan_reduced_rate(sf, bandwidth) -> bool:
+    """LoRaWAN's low-data-rate rule: on where the symbol time 2^SF / bandwidth is at least 16 ms (SF11 and SF12 at 125 kHz)."""
+    return (1 << int(sf)) / float(bandwidth) >= 16e-3
+
+
+class multi_sf_gateway_receiver(_MsgBlock):
+    """A gateway's receiver for every spreading factor at once: one wide-band capture -> the polyphase filter bank, run once per
+    step, whose rows go straight into one decoder mux per SF on the device (capi.Gateway, include/lora_hip_gateway.h).
+    Each frame is published unchanged on "frames", as (grid_index, blob) on "channel_frames" and as (grid_index, sf, blob) on
+    "sf_frames"; per (channel, SF) the frames are gateway_receiver(sf=SF)'s on the same capture.
+    reduced_rate: None = LoRaWAN's rule per SF (lorawan_reduced_rate), a bool for every SF, or a dict {sf: bool}."""
+
+    def __init__(self, samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sfs=(7, 8, 9, 10, 11, 12), implicit=False, cr=4,
+                 crc=True, reduced_rate=None, decimation=1, device=0, demod=capi.DEMOD_FFT_COMPAT, latency_ms=None):
+        super().__init__()
+        self.samp_rate = samp_rate
+        self.center_freq = center_freq
+        self.channels = [int(k) for k in channels]
+        self.sfs = [int(s) for s in sfs]
+        self.decimation = int(decimation)
+        self.device = int(device)
+        for sf in self.sfs:
+            if sf < 6 or sf > 12:  # as decoder (decoder_impl.cc:57-61)
+                sys.stderr.write("[LoRa Decoder] ERROR : Spreading factor should be between 6 and 12 (inclusive)!\n"
+                                 "                       Other values are currently not supported.\n")
+                raise SystemExit(1)
+
+        def ldro(sf):
+            if reduced_rate is None:
+                return lorawan_reduced_rate(sf, bandwidth)
+            if isinstance(reduced_rate, dict):
+                return bool(reduced_rate.get(sf, lorawan_reduced_rate(sf, bandwidth)))
+            return bool(reduced_rate)
+
+        self.reduced_rate = {sf: ldro(sf) for sf in self.sfs}
+        decoders = [dict(sf=sf, implicit=implicit, cr=cr, crc=crc, reduced_rate=self.reduced_rate[sf], demod=demod) for sf in self.sfs]
+        self.gateway = capi.Gateway(samp_rate, grid_offset, n_grid, self.channels, bandwidth, decoders, self.decimation, device)
+        if latency_ms is not None:
+            self.gateway.set_latency(float(latency_ms))
+        self.message_port_register_out("frames")
+        self.message_port_register_out("channel_frames")
+        self.message_port_register_out("sf_frames")
+
+    def work(self, input_items) -> int:
+        """numpy complex64 (host), or a torch CUDA tensor (complex64, or float32 interleaved) read on the current stream."""
+        if hasattr(input_items, "is_cuda") and input_items.is_cuda:
+            import torch
+            t = input_items.contiguous()
+            if t.device.index != self.device:
+                raise ValueError("multi_sf_gateway_receiver.work: the tensor is on %s, the gateway on cuda:%d" % (t.device, self.device))
+            if t.dtype == torch.complex64:
+                n = t.numel()
+            elif t.dtype == torch.float32:
+                if t.numel() % 2:
+                    raise ValueError("multi_sf_gateway_receiver.work: a float32 tensor holds interleaved I/Q pairs, not %d floats" % t.numel())
+                n = t.numel() // 2
+            else:
+                raise TypeError("multi_sf_gateway_receiver.work: a device tensor must be complex64 or float32 interleaved, not %s" % t.dtype)
+            self.gateway.work_device(t.data_ptr(), n, torch.cuda.current_stream(t.device).cuda_stream)
+        else:
+            x = np.asarray(input_items, dtype=np.complex64)
+            n = x.size
+            self.gateway.work(x)
+        self._publish()
+        return n
+
+    def stop(self):
+        self.gateway.flush()
+        self._publish()
+
+    def stats(self) -> dict:
+        return self.gateway.stats()
+
+    def _publish(self):
+        for blob, info in self.gateway.drain():
+            self.message_port_pub("frames", blob)
+            self.message_port_pub("channel_frames", (info.grid_index, blob))
+            self.message_port_pub("sf_frames", (info.grid_index, info.sf, blob))
+
+    def close(self):
+        self.gateway.close()
 
 
 class lora_receiver(_MsgBlock):

@@ -28,6 +28,7 @@ extern "C" {
 #define LORA_HIP_FILTERBANK_MAX_GRID 256u      /* 1 <= n_grid <= 256 */
 #define LORA_HIP_FILTERBANK_MAX_DECIMATION 1024u /* 1 <= decimation <= 1024 */
 #define LORA_HIP_FILTERBANK_MAX_TAPS 16384u    /* tap count of the low-pass design (16 Msps at the defaults: 3 855) */
+#define LORA_HIP_FILTERBANK_MAX_DST 8u         /* 1 <= n_dst <= 8 destinations per row (run_device_rows) */
 
 typedef struct lora_hip_filterbank_config {
     uint32_t       struct_size;
@@ -64,6 +65,16 @@ size_t          lora_hip_filterbank_output_items(const lora_hip_filterbank_t *h,
  * launch per call; synchronous on return.                                                                           */
 lora_hip_status lora_hip_filterbank_run_device(lora_hip_filterbank_t *h, const void *d_in, size_t n_in, void *d_out,
                                                size_t out_stride, size_t *n_out, void *hip_stream);
+
+/* Same stream, each row stored to n_dst destinations (1 .. LORA_HIP_FILTERBANK_MAX_DST) instead of one 2-D buffer:
+ * row_ptrs is a HOST array of n_dst * n_channels device pointers, row_ptrs[dst * n_channels + c] = where row c's first new item
+ * goes for destination dst (any stride between them, any offset, 8-byte aligned).  Every destination receives the same bits
+ * as lora_hip_filterbank_run_device's row.  The caller chooses n_in (lora_hip_filterbank_output_items tells what it yields)
+ * and the call consumes all of it; max_out bounds the items written per row: LORA_HIP_ERR_OVERFLOW, with *n_out set and
+ * nothing run, when n_in would yield more.  Argument checks (LORA_HIP_ERR_ARG: a NULL or misaligned pointer, n_dst out of
+ * range) come before any device call.  The history update stays on the device for any n_in.  Synchronous on return. */
+lora_hip_status lora_hip_filterbank_run_device_rows(lora_hip_filterbank_t *h, const void *d_in, size_t n_in, void *const *row_ptrs,
+                                                    uint32_t n_dst, size_t max_out, size_t *n_out, void *hip_stream);
 
 /* Same with host buffers: in = n_in cf32, out = n_channels rows of out_stride cf32. */
 lora_hip_status lora_hip_filterbank_work(lora_hip_filterbank_t *h, const float *in, size_t n_in, float *out,

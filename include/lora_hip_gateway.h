@@ -1,0 +1,99 @@
+/*
+ * lora_hip_gateway.h -- C ABI of the multi-SF gateway: one wide-band capture -> the polyphase filter bank
+ * (include/lora_hip_filterbank.h) -> one decoder per spreading factor on every channel of the band plan, on the device.
+ *
+ * The filter bank runs once per step.  Its DFT stage stores each channel's row straight into the input chunks of one
+ * lora_hip_mux per decoder config (lora_hip_filterbank_run_device_rows); nothing returns to the host until frames are
+ * published.  Per (row, decoder) pair the frames are those of a lora_hip_mux with that decoder config fed that row, which are
+ * those of the single decoder on the same row.
+ * Plain C types only; device pointers and the HIP stream travel as void*.  Same conventions as lora_hip.h.
+ */
+#ifndef LORA_HIP_GATEWAY_H
+#define LORA_HIP_GATEWAY_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "lora_hip.h"
+#include "lora_hip_filterbank.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LORA_HIP_GATEWAY_MAX_DECODERS 7u      /* SF6..SF12, one decoder each at most */
+#define LORA_HIP_GATEWAY_STEP_OUTPUTS 65536u  /* filter-bank outputs per row and step; every decoder's batch is a multiple of it */
+
+typedef struct lora_hip_gateway_config {
+    uint32_t                     struct_size;
+    lora_hip_filterbank_config_t filterbank;  /* the band plan; its channels are the rows every decoder sees        */
+    const lora_hip_config_t     *decoders;    /* one per spreading factor: sf, cr, crc, implicit, reduced_rate, demod */
+    uint32_t                     n_decoders;  /* 1 .. LORA_HIP_GATEWAY_MAX_DECODERS                                  */
+    uint32_t                     flags;       /* reserved, 0                                                          */
+} lora_hip_gateway_config_t;
+
+/* Where a published frame came from. */
+typedef struct lora_hip_gateway_frame_info {
+    uint32_t row;         /* filter-bank row (index into filterbank.channels)                                 */
+    int32_t  grid_index;  /* filterbank.channels[row]                                                          */
+    uint32_t sf;          /* the decoder's spreading factor                                                    */
+    uint32_t decoder;     /* index into decoders                                                               */
+    uint32_t length;      /* blob length in bytes                                                              */
+    uint32_t reserved;
+    int64_t  header_pos;  /* sample index, in that row's samples, of the first header symbol (as the mux)      */
+    int64_t  end_pos;     /* sample index just after the last consumed payload symbol                         */
+} lora_hip_gateway_frame_info_t;
+
+typedef struct lora_hip_gateway_stats {
+    uint32_t struct_size;
+    uint32_t n_decoders;
+    uint64_t passes[LORA_HIP_GATEWAY_MAX_DECODERS];             /* device passes per decoder                      */
+    uint64_t passes_by_latency[LORA_HIP_GATEWAY_MAX_DECODERS];  /* ... of which the latency bound launched         */
+    uint64_t filterbank_calls;                                  /* filter-bank launches (one per step)           */
+    double   filterbank_ms;                                     /* their kernel time, summed (HIP events)        */
+    uint64_t items_in;                                          /* wide-band items taken by work / work_device   */
+    uint64_t step_outputs;                                      /* LORA_HIP_GATEWAY_STEP_OUTPUTS                  */
+} lora_hip_gateway_stats_t;
+
+typedef struct lora_hip_gateway lora_hip_gateway_t;
+
+/* LORA_HIP_ERR_ARG: cfg/out/decoders NULL, a struct_size too small (a decoder's must equal sizeof(lora_hip_config_t)),
+ * filterbank.channels NULL; LORA_HIP_ERR_BAD_SF: a decoder's sf outside 6..12; LORA_HIP_ERR_BAD_CONFIG: n_decoders 0 or above
+ * the limit, flags != 0, two decoders with one sf, a decoder whose samp_rate is not (float)(filterbank.samp_rate /
+ * filterbank.decimation) or whose bandwidth or device differs from the filter bank's, cr > 4, an unknown demod, a batch_items that
+ * is not a multiple of LORA_HIP_GATEWAY_STEP_OUTPUTS (0 = automatic: the mux's own, rounded up to such a multiple), or a
+ * filter-bank limit (lora_hip_filterbank_create).  All of these before any device call; then LORA_HIP_ERR_NO_DEVICE without a
+ * device.  The buffers are allocated here: per decoder two chunks of n_channels * (tail area + batch) items.
+ * Like lora_hip_mux, a decoder grows both of its chunks at run time when a packet is longer than its tail area (= batch: at SF12
+ * on 1 Msps rows, 2^21 samples, about 2.1 s of air). */
+lora_hip_status lora_hip_gateway_create(const lora_hip_gateway_config_t *cfg, lora_hip_gateway_t **out);
+void            lora_hip_gateway_destroy(lora_hip_gateway_t *g);
+const char     *lora_hip_gateway_last_error(const lora_hip_gateway_t *g);
+
+/* n cf32 wide-band items from host memory, uploaded once.  The filter bank runs in steps of LORA_HIP_GATEWAY_STEP_OUTPUTS outputs
+ * per row; input short of a whole step is gathered on the device until it is one, and flush runs the rest.  So any chunking gives
+ * the same rows, bit for bit, and the same frames and positions. */
+lora_hip_status lora_hip_gateway_work(lora_hip_gateway_t *g, const float *iq, size_t n);
+
+/* The same for n cf32 items already in device memory, read after the work queued so far on hip_stream.  The caller may reuse
+ * the buffer when the call returns. */
+lora_hip_status lora_hip_gateway_work_device(lora_hip_gateway_t *g, const void *d_iq, size_t n, void *hip_stream);
+
+/* End of stream: the last partial step, then every decoder decodes what it holds.  The handle stays usable: input after a flush
+ * continues the stream (the first step after it may be shorter, so that the steps line up with the decoders' chunks again). */
+lora_hip_status lora_hip_gateway_flush(lora_hip_gateway_t *g);
+/* lora_hip_mux_set_latency on every decoder. */
+lora_hip_status lora_hip_gateway_set_latency(lora_hip_gateway_t *g, float max_latency_ms);
+
+/* Frames: per (row, decoder) pair in the single decoder's order; across pairs unspecified.  The blob is the decoder's blob
+ * unchanged; row and spreading factor travel in info. */
+size_t          lora_hip_gateway_frames_available(const lora_hip_gateway_t *g);
+lora_hip_status lora_hip_gateway_poll_frame(lora_hip_gateway_t *g, uint8_t *buf, size_t cap, size_t *len, lora_hip_gateway_frame_info_t *info);
+
+/* stats->struct_size must be set by the caller. */
+lora_hip_status lora_hip_gateway_stats(const lora_hip_gateway_t *g, lora_hip_gateway_stats_t *stats);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* LORA_HIP_GATEWAY_H */
