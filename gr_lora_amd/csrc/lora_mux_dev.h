@@ -1,6 +1,7 @@
 // lora_mux_dev.h -- internal: the mux's device-fed path (lora_runtime.cpp), next to lora_hip_mux_work's host uploads.
 // A writer on the device (the gateway's filter bank, lora_gateway.cpp) stores the next n items of every channel straight into
-// the mux's current chunks; the mux then runs the same pass loop and latency check as after lora_hip_mux_work.  Per step:
+// the current chunks of the mux's pipeline (the chunk pipeline of lora_hip_work, with n channels); the mux then
+// runs the same pass loop and latency check as after lora_hip_mux_work.  Per step:
 //     collect_if_done -> room -> rows -> before_write(st) -> the writer on st -> event on st -> commit(n, event)
 // Row pointers stay valid until the next commit or collect_if_done (a rotation or a grown tail area moves them).
 // Not exported (hidden visibility): the C ABI is include/lora_hip.h and include/lora_hip_gateway.h.

@@ -98,6 +98,29 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// The streaming pipeline under lora_hip_work (one channel) and lora_hip_mux (n channels): see the description above pipe_init().
+struct ChunkPipe {
+    struct Chan {
+        size_t fill = 0, tail_len = 0; // items of the chunk being filled uploaded (or queued for upload) so far; items carried over in front of it
+        uint32_t cr = 0;               // decoder state carried from pass to pass: d_phdr.cr, power queue,
+        PwrState pwr;
+        int64_t host_base = 0;         // ... and the absolute item index of the first item of the channel's next stream region
+    };
+    std::vector<Chan> ch;
+    DevBuf<float2> dbuf[2];            // per channel a region [ tail area (tailcap items, right-aligned) | chunk (batch items) ]
+    int cur = 0;                       // buffer whose chunks are being filled
+    size_t batch = 0, tailcap = 0, region = 0;
+    hipStream_t copy_st = nullptr, comp_st = nullptr;
+    hipEvent_t up_ev = nullptr, tail_ev = nullptr;
+    bool inflight = false;             // a pass is running on dbuf[cur ^ 1]
+    // latency bound: a pass is launched when the oldest unlaunched sample has waited this long
+    float max_latency_ms = 50.0f;
+    std::chrono::steady_clock::time_point t_first; // arrival of the first item of the chunks being filled
+    bool have_first = false;
+    uint64_t passes = 0, passes_by_latency = 0;
+    float2 *row(size_t c) const { return dbuf[cur].p + c * region + tailcap + ch[c].fill; } // where channel c's next item goes
+};
+
 } // namespace
 
 struct lora_hip_decoder {
@@ -158,34 +181,16 @@ struct lora_hip_decoder {
     std::vector<lora_hip_step_t> trace;
     lora_hip_timing_t timing{};
     std::string err;
-    // streaming state (lora_hip_work): see the pipeline description above stream_rotate()
-    struct StreamPipe {
-        DevBuf<float2> dbuf[2];       // [ tail (up to tailcap items, right-aligned) | chunk (batch items) ]
-        size_t tailcap = 0;
-        int cur = 0;                  // buffer whose chunk is being filled
-        size_t fill = 0;              // items of the current chunk uploaded (or queued for upload) so far
-        size_t tail_len = 0;          // items carried over in front of the current chunk
-        hipStream_t copy_st = nullptr, comp_st = nullptr;
-        hipEvent_t up_ev = nullptr, tail_ev = nullptr;
-        bool inflight = false;        // a pass is running on dbuf[cur ^ 1]
-        size_t fl_off = 0, fl_len = 0;
-        PinnedBuf<float2> stage[2];   // bounce buffers for caller memory that is not page-locked
+    // streaming: the chunk pipeline (one channel for lora_hip_work, whose first call creates its device side; n for a mux)
+    ChunkPipe pipe;
+    struct HostFeed {                  // lora_hip_work's uploads into it
+        PinnedBuf<float2> stage[2];    // bounce buffers for caller memory that is not page-locked
         hipEvent_t stage_ev[2] = {nullptr, nullptr};
         bool stage_busy[2] = {false, false};
         int stage_i = 0;
         std::vector<std::pair<uintptr_t, uintptr_t>> pinned; // caller ranges registered with hipHostRegister (DMA straight from them)
         std::vector<std::pair<uintptr_t, uintptr_t>> refused; // ranges the runtime would not register: do not ask again
-        uint64_t bytes_direct = 0, bytes_staged = 0;
-        // latency bound (lora_hip_set_stream_latency): a pass is launched when the oldest unlaunched sample has waited this long
-        float max_latency_ms = 50.0f;
-        std::chrono::steady_clock::time_point t_first; // arrival of the first item of the chunk being filled
-        bool have_first = false;
-        uint64_t passes = 0, passes_by_latency = 0;
-    } sp;
-    int64_t host_base = 0;      // absolute item index of the first item of the stream region of the next pass
-    uint32_t stream_cr = 0;
-    PwrState stream_pwr;
-    size_t batch_items = 0;
+    } feed;
     const char *last_kernel = nullptr; // name of the walker kernel the last pass's main launch ran
     uint32_t last_kernel_jobs = 0;     // ... and its job count (reset when a pass begins)
     uint32_t resident_slots = 0;
@@ -938,12 +943,180 @@ struct DeviceEnv {
     double walker_ms() const { return h->timing.walker_ms; }
 };
 
-lora_hip_status decode_streams(lora_hip_decoder *h, const float2 *d_iq, std::vector<StreamDesc> &streams, hipStream_t st)
+// the status of a failed scheduler call: that of the HIP call that left a message, else an internal error
+lora_hip_status scheduler_failed(lora_hip_decoder *h)
 {
-    DeviceEnv env{h, d_iq, st};
-    const int rc = lora_hip::decode_streams(env, streams);
-    if (rc == 0) return LORA_HIP_OK;
+    h->pending.open = false;
     return h->err.empty() ? fail(h, LORA_HIP_ERR_INTERNAL, "scheduler failed") : LORA_HIP_ERR_HIP;
+}
+
+// A pass over h->pass_streams of d_iq, launched on st (pass_begin) and collected (pass_end): lora_hip_decode_device_begin / _end and
+// the streaming pipeline.
+lora_hip_status pass_begin(lora_hip_decoder *h, const float2 *d_iq, hipStream_t st, bool iq_ready)
+{
+    h->pass_iq = d_iq; h->pass_st = st;
+    h->iq_ready = iq_ready;
+    h->err.clear();
+    DeviceEnv env{h, d_iq, st};
+    const int rc = lora_hip::decode_begin(env, h->pass_streams, h->pass);
+    h->iq_ready = false;
+    if (rc != 0) return scheduler_failed(h);
+    h->pass_open = true;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status pass_end(lora_hip_decoder *h)
+{
+    h->pass_open = false;
+    h->err.clear();
+    DeviceEnv env{h, h->pass_iq, h->pass_st};
+    return lora_hip::decode_end(env, h->pass_streams, h->pass) == 0 ? LORA_HIP_OK : scheduler_failed(h);
+}
+
+// ---- the streaming pipeline: lora_hip_work's stream, or a mux's channels, in chunks decoded while the next ones arrive ------------
+// Every channel is cut into chunks of `batch` items.  Samples are uploaded as they arrive (asynchronously, on copy_st) into the
+// channel's chunk area in one of two device buffers; a rotation collects the pass over the other buffer (decoder state, frames, the
+// undecoded tails), copies each tail in front of its channel's new chunk (device to device), and launches the pass over
+// [tail | chunk] of every channel on comp_st - so the device decodes one chunk while the next is being uploaded, and the host only
+// ever waits for a kernel that had a whole chunk's arrival time to finish.  Frames surface one chunk later than in a synchronous
+// pass; a flush drains everything.  Output is what one pass over each whole stream would give
+// (tests/test_gpu_parity.py::test_streaming_*, tests/test_gpu_mux.py).  The feeders own their upload policy and when to rotate:
+// lora_hip_work (pinned bounce buffers or DMA from the caller's memory, a rotation per full chunk), lora_hip_mux_work and the
+// device-fed path (lora_mux_dev.h: a rotation when every channel's chunk is full, or one channel's host surplus is too far ahead).
+
+// n_channels of `batch`-item chunks (host side; pipe_open creates the device side)
+void pipe_init(lora_hip_decoder *h, uint32_t n_channels, size_t batch)
+{
+    ChunkPipe &p = h->pipe;
+    p.ch.assign(n_channels, ChunkPipe::Chan{});
+    for (ChunkPipe::Chan &c : p.ch) c.cr = h->P.ctor_cr;
+    p.batch = batch;
+    p.tailcap = std::max<size_t>(batch, 4u * (size_t)h->P.sps);
+    p.region = p.tailcap + batch;
+}
+
+lora_hip_status pipe_open(lora_hip_decoder *h)
+{
+    ChunkPipe &p = h->pipe;
+    if (p.copy_st) return LORA_HIP_OK;
+    HIP_TRY(h, hipStreamCreateWithFlags(&p.copy_st, hipStreamNonBlocking));
+    HIP_TRY(h, hipStreamCreateWithFlags(&p.comp_st, hipStreamNonBlocking));
+    HIP_TRY(h, hipEventCreateWithFlags(&p.up_ev, hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&p.tail_ev, hipEventDisableTiming));
+    for (int i = 0; i < 2; i++) HIP_TRY(h, p.dbuf[i].reserve(p.ch.size() * p.region));
+    return LORA_HIP_OK;
+}
+
+// some channel holds new samples, and enough for a pass (:91: two symbols)
+bool pipe_launchable(const lora_hip_decoder *h)
+{
+    for (const ChunkPipe::Chan &c : h->pipe.ch)
+        if (c.fill != 0 && c.tail_len + c.fill >= 2u * (size_t)h->P.sps) return true;
+    return false;
+}
+
+// the latency bound: the oldest sample not yet handed to a pass has waited long enough (and a pass could run at all)
+bool pipe_latency_due(const lora_hip_decoder *h)
+{
+    const ChunkPipe &p = h->pipe;
+    return p.max_latency_ms > 0.0f && p.have_first && pipe_launchable(h) &&
+           std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - p.t_first).count() >= p.max_latency_ms;
+}
+
+// collects the pass in flight: per channel its decoder state, its frames (published through the handle's queue) and its tail
+lora_hip_status pipe_collect(lora_hip_decoder *h)
+{
+    ChunkPipe &p = h->pipe;
+    if (!p.inflight) return LORA_HIP_OK;
+    p.inflight = false;
+    const lora_hip_status s = pass_end(h);
+    if (s != LORA_HIP_OK) return s;
+    bool any_tail = false;
+    for (const StreamDesc &sd : h->pass_streams) {
+        ChunkPipe::Chan &c = p.ch[sd.id];
+        c.cr = sd.cr_out; c.pwr = sd.pwr;
+        const size_t keep_from = (size_t)std::min<int64_t>(std::max<int64_t>(sd.final_pos, 0), (int64_t)sd.len);
+        const size_t tail = sd.len - keep_from; // an attempt that ran out of data is re-run from its start with the next chunk behind it
+        c.host_base += (int64_t)keep_from;
+        if (tail > p.tailcap) { // a packet longer than the tail area: grow both buffers, every region keeps its chunk and the right end of its tail area
+            const size_t ncap = std::max(2u * p.tailcap, tail + (size_t)h->P.sps), nregion = ncap + p.batch;
+            HIP_TRY(h, hipStreamSynchronize(p.copy_st));
+            HIP_TRY(h, hipStreamSynchronize(p.comp_st));
+            for (int i = 0; i < 2; i++) {
+                DevBuf<float2> nb;
+                HIP_TRY(h, nb.reserve(p.ch.size() * nregion));
+                for (size_t q = 0; q < p.ch.size(); q++)
+                    HIP_TRY(h, hipMemcpyAsync(nb.p + q * nregion + (ncap - p.tailcap), p.dbuf[i].p + q * p.region, p.region * sizeof(float2), hipMemcpyDeviceToDevice, p.comp_st));
+                HIP_TRY(h, hipStreamSynchronize(p.comp_st));
+                std::swap(p.dbuf[i], nb);
+                nb.release();
+            }
+            for (StreamDesc &x : h->pass_streams) x.off = (x.off / p.region) * nregion + (x.off % p.region) + (ncap - p.tailcap);
+            p.tailcap = ncap; p.region = nregion;
+        }
+        if (tail) {
+            HIP_TRY(h, hipMemcpyAsync(p.dbuf[p.cur].p + (size_t)sd.id * p.region + p.tailcap - tail, p.dbuf[p.cur ^ 1].p + sd.off + keep_from, tail * sizeof(float2),
+                                      hipMemcpyDeviceToDevice, p.comp_st));
+            any_tail = true;
+        }
+        c.tail_len = tail;
+    }
+    if (any_tail) { // the sources sit in chunk areas the next uploads overwrite: they wait for these copies
+        HIP_TRY(h, hipEventRecord(p.tail_ev, p.comp_st));
+        HIP_TRY(h, hipStreamWaitEvent(p.copy_st, p.tail_ev, 0));
+    }
+    return LORA_HIP_OK;
+}
+
+// ... if its device work is done (hipEventQuery: no waiting) - its frames are published by this call, not a rotation later
+lora_hip_status pipe_collect_if_done(lora_hip_decoder *h)
+{
+    lora_hip_status s = LORA_HIP_OK;
+    if (h->pipe.inflight && h->pending.open && hipEventQuery(h->ev_done) == hipSuccess) s = pipe_collect(h);
+    (void)hipGetLastError(); // (hipErrorNotReady of the query)
+    return s;
+}
+
+// the chunks being filled are complete (or the latency bound or a flush cuts them short): collects the pass in flight, then launches
+// one over what every channel holds.  A channel shorter than two symbols (:91) stays out of the pass; its samples move along to the
+// new buffer.  Nothing is launched when no channel has enough: the same chunks go on filling.
+lora_hip_status pipe_rotate(lora_hip_decoder *h, bool by_latency)
+{
+    ChunkPipe &p = h->pipe;
+    HIP_TRY(h, hipEventRecord(p.up_ev, p.copy_st));
+    lora_hip_status s = pipe_collect(h);
+    if (s != LORA_HIP_OK) return s;
+    std::vector<StreamDesc> &sds = h->pass_streams;
+    sds.clear();
+    for (uint32_t c = 0; c < p.ch.size(); c++) {
+        ChunkPipe::Chan &C = p.ch[c];
+        const size_t len = C.tail_len + C.fill;
+        if (len < 2u * (size_t)h->P.sps) continue;
+        StreamDesc sd{};
+        sd.off = (uint64_t)c * p.region + p.tailcap - C.tail_len; sd.len = len; sd.id = c;
+        sd.cr_in = C.cr; sd.pwr = C.pwr; sd.abs_base = C.host_base;
+        sds.push_back(sd);
+    }
+    if (sds.empty()) return LORA_HIP_OK;
+    HIP_TRY(h, hipStreamWaitEvent(p.comp_st, p.up_ev, 0));
+    h->timing = lora_hip_timing_t{};
+    for (const StreamDesc &sd : sds) h->timing.items += sd.len;
+    s = pass_begin(h, p.dbuf[p.cur].p, p.comp_st, false);
+    if (s != LORA_HIP_OK) return s;
+    p.inflight = true;
+    p.passes++; p.passes_by_latency += by_latency ? 1u : 0u;
+    p.cur ^= 1;
+    p.have_first = false;
+    for (uint32_t c = 0; c < p.ch.size(); c++) {
+        ChunkPipe::Chan &C = p.ch[c];
+        const size_t len = C.tail_len + C.fill;
+        const bool in_pass = len >= 2u * (size_t)h->P.sps;
+        if (!in_pass && len)
+            HIP_TRY(h, hipMemcpyAsync(p.dbuf[p.cur].p + (size_t)c * p.region + p.tailcap - len, p.dbuf[p.cur ^ 1].p + (size_t)c * p.region + p.tailcap - C.tail_len,
+                                      len * sizeof(float2), hipMemcpyDeviceToDevice, p.copy_st));
+        C.tail_len = in_pass ? 0 : len; C.fill = 0;
+    }
+    return LORA_HIP_OK;
 }
 
 } // namespace
@@ -970,8 +1143,6 @@ const char *lora_hip_strerror(lora_hip_status s)
 }
 
 const char *lora_hip_last_error(const lora_hip_decoder_t *h) { return h ? h->err.c_str() : g_create_err.c_str(); }
-
-static void stream_pipe_release(lora_hip_decoder *h);
 
 lora_hip_status lora_hip_create(const lora_hip_config_t *cfg, lora_hip_decoder_t **out)
 {
@@ -1000,8 +1171,7 @@ lora_hip_status lora_hip_create(const lora_hip_config_t *cfg, lora_hip_decoder_t
                              hipEventCreate(&h->ev_pay1) != hipSuccess || hipEventCreate(&h->ev_pay_done) != hipSuccess))
         s = LORA_HIP_ERR_HIP;
     if (s != LORA_HIP_OK) { lora_hip_destroy(h); return s; }
-    h->stream_cr = h->P.ctor_cr;
-    h->batch_items = cfg->batch_items ? cfg->batch_items : std::max<size_t>(1u << 20, 64ull * h->P.sps);
+    pipe_init(h, 1, cfg->batch_items ? cfg->batch_items : std::max<size_t>(1u << 20, 64ull * h->P.sps));
     *out = h;
     return LORA_HIP_OK;
 }
@@ -1010,7 +1180,7 @@ void lora_hip_destroy(lora_hip_decoder_t *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->sp.comp_st) { (void)hipStreamSynchronize(h->sp.copy_st); (void)hipStreamSynchronize(h->sp.comp_st); } // a streaming pass may be in flight
+    if (h->pipe.comp_st) { (void)hipStreamSynchronize(h->pipe.copy_st); (void)hipStreamSynchronize(h->pipe.comp_st); } // a streaming pass may be in flight
     if (h->d_down) (void)hipFree(h->d_down);
     if (h->d_twN) (void)hipFree(h->d_twN);
     if (h->d_tws) (void)hipFree(h->d_tws);
@@ -1024,13 +1194,15 @@ void lora_hip_destroy(lora_hip_decoder_t *h)
     h->p_pay_off.release(); h->p_pay_desc.release(); h->p_pay_out.release(); h->d_fine.release(); h->d_alt_shift.release(); h->d_alt_bins.release(); h->d_alt_fine.release();
     h->d_jobs.release(); h->d_results.release(); h->d_recs.release(); h->d_scratch.release();
     h->d_trace.release(); h->d_staging.release(); h->d_offsets.release(); h->d_bins.release();
-    stream_pipe_release(h);
+    for (auto &r : h->feed.pinned) (void)hipHostUnregister((void *)r.first);
+    for (int i = 0; i < 2; i++) { h->pipe.dbuf[i].release(); h->feed.stage[i].release(); }
     h->p_jobs.release(); h->p_res.release(); h->p_recs.release();
     h->d_balance.release(); h->d_env_E.release(); h->d_env_buf.release(); h->p_env_streams.release(); h->p_env_buf.release();
-    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_done, h->ev_pre0, h->ev_pre1, h->ev_dep, h->ev_pay0, h->ev_pay1, h->ev_pay_done})
+    for (hipEvent_t e : {h->ev0, h->ev1, h->ev_done, h->ev_pre0, h->ev_pre1, h->ev_dep, h->ev_pay0, h->ev_pay1, h->ev_pay_done, h->pipe.up_ev, h->pipe.tail_ev,
+                         h->feed.stage_ev[0], h->feed.stage_ev[1]})
         if (e) (void)hipEventDestroy(e);
-    if (h->pre_stream) (void)hipStreamDestroy(h->pre_stream);
-    if (h->pay_stream) (void)hipStreamDestroy(h->pay_stream);
+    for (hipStream_t st : {h->pre_stream, h->pay_stream, h->pipe.copy_st, h->pipe.comp_st})
+        if (st) (void)hipStreamDestroy(st);
     delete h;
 }
 
@@ -1099,15 +1271,7 @@ lora_hip_status lora_hip_decode_device_begin(lora_hip_decoder_t *h, const void *
         sds[i].cr_in = h->P.ctor_cr; sds[i].abs_base = 0;
         h->timing.items += stream_len[i];
     }
-    h->pass_iq = (const float2 *)d_iq; h->pass_st = (hipStream_t)hip_stream;
-    h->iq_ready = (flags & LORA_HIP_BEGIN_IQ_READY) != 0u;
-    h->err.clear();
-    DeviceEnv env{h, h->pass_iq, h->pass_st};
-    const int rc = lora_hip::decode_begin(env, sds, h->pass);
-    h->iq_ready = false;
-    if (rc != 0) { h->pending.open = false; return h->err.empty() ? fail(h, LORA_HIP_ERR_INTERNAL, "scheduler failed") : LORA_HIP_ERR_HIP; }
-    h->pass_open = true;
-    return LORA_HIP_OK;
+    return pass_begin(h, (const float2 *)d_iq, (hipStream_t)hip_stream, (flags & LORA_HIP_BEGIN_IQ_READY) != 0u);
 }
 
 lora_hip_status lora_hip_decode_device_prepass(lora_hip_decoder_t *h, const void *d_iq, size_t total_items, const uint64_t *stream_off,
@@ -1137,14 +1301,9 @@ lora_hip_status lora_hip_decode_device_end(lora_hip_decoder_t *h)
     if (!h->pass_open) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_decode_device_end without a pass begun");
     // (the streaming pipeline keeps its in-flight pass in the same PassCtx: collecting it here would leave lora_hip_work's tail,
     // d_phdr.cr and power queue behind - that pass belongs to lora_hip_work / lora_hip_flush)
-    if (h->sp.inflight) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_decode_device_end: the open pass is lora_hip_work's; call lora_hip_flush");
-    h->pass_open = false;
+    if (h->pipe.inflight) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_decode_device_end: the open pass is lora_hip_work's; call lora_hip_flush");
     HIP_TRY(h, hipSetDevice(h->device));
-    h->err.clear();
-    DeviceEnv env{h, h->pass_iq, h->pass_st};
-    const int rc = lora_hip::decode_end(env, h->pass_streams, h->pass);
-    if (rc != 0) { h->pending.open = false; return h->err.empty() ? fail(h, LORA_HIP_ERR_INTERNAL, "scheduler failed") : LORA_HIP_ERR_HIP; }
-    return LORA_HIP_OK;
+    return pass_end(h);
 }
 
 lora_hip_status lora_hip_decode_device(lora_hip_decoder_t *h, const void *d_iq, size_t total_items,
@@ -1180,52 +1339,18 @@ lora_hip_status lora_hip_gap_starts_device(lora_hip_decoder_t *h, const void *d_
     return LORA_HIP_OK;
 }
 
-// ---- lora_hip_work: the reference block's work() contract (host buffers in, frames out), pipelined ------------------
-// The stream is cut into chunks of batch_items.  Samples are uploaded AS THEY ARRIVE (asynchronously, on a copy stream of
-// the handle) into the chunk area of one of two device buffers; when a chunk is full, the pass over the previous chunk is
-// collected (state, frames, the undecoded tail), the tail is copied in front of the new chunk (device to device), and the
-// pass over [tail | chunk] is launched - so the device decodes chunk k while chunk k + 1 is being uploaded and the host
-// only ever waits for a kernel that had a whole chunk's arrival time to finish.  Frames surface one chunk later than in
-// a synchronous pass; lora_hip_flush() drains everything.  Caller memory that is page-locked (or that hipHostRegister
-// accepts: GNU Radio's buffers are long-lived) is DMA'd from directly; anything else goes through two pinned bounce
-// buffers.  Output is what one pass over the whole stream would give (tests/test_gpu_parity.py::test_streaming_*).
-static void stream_pipe_release(lora_hip_decoder *h)
-{
-    auto &sp = h->sp;
-    for (auto &r : sp.pinned) (void)hipHostUnregister((void *)r.first);
-    sp.pinned.clear(); sp.refused.clear();
-    for (int i = 0; i < 2; i++) {
-        sp.dbuf[i].release(); sp.stage[i].release();
-        if (sp.stage_ev[i]) { (void)hipEventDestroy(sp.stage_ev[i]); sp.stage_ev[i] = nullptr; }
-    }
-    if (sp.up_ev) { (void)hipEventDestroy(sp.up_ev); sp.up_ev = nullptr; }
-    if (sp.tail_ev) { (void)hipEventDestroy(sp.tail_ev); sp.tail_ev = nullptr; }
-    if (sp.copy_st) { (void)hipStreamDestroy(sp.copy_st); sp.copy_st = nullptr; }
-    if (sp.comp_st) { (void)hipStreamDestroy(sp.comp_st); sp.comp_st = nullptr; }
-}
-
-static lora_hip_status stream_pipe_init(lora_hip_decoder *h)
-{
-    auto &sp = h->sp;
-    if (sp.copy_st) return LORA_HIP_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamCreateWithFlags(&sp.copy_st, hipStreamNonBlocking));
-    HIP_TRY(h, hipStreamCreateWithFlags(&sp.comp_st, hipStreamNonBlocking));
-    HIP_TRY(h, hipEventCreateWithFlags(&sp.up_ev, hipEventDisableTiming));
-    HIP_TRY(h, hipEventCreateWithFlags(&sp.tail_ev, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) HIP_TRY(h, hipEventCreateWithFlags(&sp.stage_ev[i], hipEventDisableTiming));
-    sp.tailcap = std::max<size_t>(h->batch_items, 4u * (size_t)h->P.sps);
-    for (int i = 0; i < 2; i++) HIP_TRY(h, sp.dbuf[i].reserve(sp.tailcap + h->batch_items));
-    return LORA_HIP_OK;
-}
+// ---- lora_hip_work: the reference block's work() contract (host buffers in, frames out) on a one-channel pipeline ----------
+// (the pipeline: above pipe_init).  A pass is launched per full chunk.  Caller memory that is page-locked (or that
+// hipHostRegister accepts: GNU Radio's buffers are long-lived) is DMA'd from directly; anything else goes through two pinned
+// bounce buffers.
 
 // is [p, p + bytes) inside memory the device can DMA from?  Tries to page-lock unknown ranges once.
 static bool stream_host_pinned(lora_hip_decoder *h, const void *p, size_t bytes)
 {
-    auto &sp = h->sp;
+    auto &f = h->feed;
     const uintptr_t a = (uintptr_t)p, b = a + bytes;
-    for (auto &r : sp.pinned) if (a >= r.first && b <= r.second) return true;
-    for (auto &r : sp.refused) if (a >= r.first && b <= r.second) return false;
+    for (auto &r : f.pinned) if (a >= r.first && b <= r.second) return true;
+    for (auto &r : f.refused) if (a >= r.first && b <= r.second) return false;
     { // hipHostMalloc'ed, or registered by the caller: both ends must be (a range registered only in part is not usable)
         hipPointerAttribute_t a0{}, a1{};
         const bool h0 = hipPointerGetAttributes(&a0, p) == hipSuccess && a0.type == hipMemoryTypeHost;
@@ -1239,149 +1364,68 @@ static bool stream_host_pinned(lora_hip_decoder *h, const void *p, size_t bytes)
     // else (a GNU Radio block's input buffer).  Without the flag, memory that is not page-locked goes through the bounce buffers.
     if (!(h->cfg.flags & LORA_HIP_FLAG_PIN_HOST) || bytes < (256u << 10)) return false; // (small calls: the bounce copy is cheaper)
     const uintptr_t pg = 4096u, ra = a & ~(pg - 1u), rb = (b + pg - 1u) & ~(pg - 1u);
-    if (hipHostRegister((void *)ra, rb - ra, hipHostRegisterDefault) == hipSuccess) { sp.pinned.emplace_back(ra, rb); return true; }
+    if (hipHostRegister((void *)ra, rb - ra, hipHostRegisterDefault) == hipSuccess) { f.pinned.emplace_back(ra, rb); return true; }
     (void)hipGetLastError();
-    sp.refused.emplace_back(a, b);
+    f.refused.emplace_back(a, b);
     return false;
-}
-
-// collects the pass in flight: decoder state, frames, and the undecoded tail moved in front of the chunk being filled
-static lora_hip_status stream_collect(lora_hip_decoder *h)
-{
-    auto &sp = h->sp;
-    if (!sp.inflight) return LORA_HIP_OK;
-    sp.inflight = false;
-    h->pass_open = false;
-    h->err.clear();
-    DeviceEnv env{h, h->pass_iq, h->pass_st};
-    const int rc = lora_hip::decode_end(env, h->pass_streams, h->pass);
-    if (rc != 0) { h->pending.open = false; return h->err.empty() ? fail(h, LORA_HIP_ERR_INTERNAL, "scheduler failed") : LORA_HIP_ERR_HIP; }
-    const StreamDesc &sd = h->pass_streams[0];
-    h->stream_cr = sd.cr_out;
-    h->stream_pwr = sd.pwr;
-    const size_t keep_from = (size_t)std::min<int64_t>(std::max<int64_t>(sd.final_pos, 0), (int64_t)sp.fl_len);
-    const size_t tail = sp.fl_len - keep_from; // an attempt that ran out of data is re-run from its start with the next chunk behind it
-    h->host_base += (int64_t)keep_from;
-    if (tail > sp.tailcap) { // (a packet longer than the tail area: grow both buffers, keeping what the filling one holds)
-        const size_t ncap = std::max(2u * sp.tailcap, tail + (size_t)h->P.sps);
-        HIP_TRY(h, hipStreamSynchronize(sp.copy_st));
-        for (int i = 0; i < 2; i++) {
-            DevBuf<float2> nb;
-            HIP_TRY(h, nb.reserve(ncap + h->batch_items));
-            HIP_TRY(h, hipMemcpyAsync(nb.p + ncap, sp.dbuf[i].p + sp.tailcap, h->batch_items * sizeof(float2), hipMemcpyDeviceToDevice, sp.comp_st));
-            if (i == (sp.cur ^ 1)) // the buffer the pass ran on: its stream region moves along (it is the source of the tail below)
-                HIP_TRY(h, hipMemcpyAsync(nb.p + ncap - (sp.tailcap - sp.fl_off), sp.dbuf[i].p + sp.fl_off, (sp.tailcap - sp.fl_off) * sizeof(float2), hipMemcpyDeviceToDevice, sp.comp_st));
-            HIP_TRY(h, hipStreamSynchronize(sp.comp_st));
-            std::swap(sp.dbuf[i], nb);
-            nb.release();
-        }
-        sp.fl_off += ncap - sp.tailcap;
-        sp.tailcap = ncap;
-    }
-    if (tail) {
-        HIP_TRY(h, hipMemcpyAsync(sp.dbuf[sp.cur].p + sp.tailcap - tail, sp.dbuf[sp.cur ^ 1].p + sp.fl_off + keep_from, tail * sizeof(float2), hipMemcpyDeviceToDevice, sp.comp_st));
-        // the source sits in the chunk area that the NEXT uploads overwrite: they wait for this copy
-        HIP_TRY(h, hipEventRecord(sp.tail_ev, sp.comp_st));
-        HIP_TRY(h, hipStreamWaitEvent(sp.copy_st, sp.tail_ev, 0));
-    }
-    sp.tail_len = tail;
-    return LORA_HIP_OK;
-}
-
-// the chunk being filled is complete (or the stream is being flushed): collect the previous pass, launch this one
-static lora_hip_status stream_rotate(lora_hip_decoder *h)
-{
-    auto &sp = h->sp;
-    HIP_TRY(h, hipEventRecord(sp.up_ev, sp.copy_st));
-    lora_hip_status s = stream_collect(h);
-    if (s != LORA_HIP_OK) return s;
-    const size_t len = sp.tail_len + sp.fill;
-    if (len >= 2u * (size_t)h->P.sps) {
-        HIP_TRY(h, hipStreamWaitEvent(sp.comp_st, sp.up_ev, 0));
-        std::vector<StreamDesc> &sds = h->pass_streams;
-        sds.assign(1, StreamDesc{});
-        sds[0].off = sp.tailcap - sp.tail_len; sds[0].len = len; sds[0].id = 0;
-        sds[0].cr_in = h->stream_cr; sds[0].pwr = h->stream_pwr; sds[0].abs_base = h->host_base;
-        h->timing = lora_hip_timing_t{};
-        h->timing.items = len;
-        h->pass_iq = sp.dbuf[sp.cur].p; h->pass_st = sp.comp_st;
-        h->err.clear();
-        DeviceEnv env{h, h->pass_iq, h->pass_st};
-        const int rc = lora_hip::decode_begin(env, sds, h->pass);
-        if (rc != 0) { h->pending.open = false; return h->err.empty() ? fail(h, LORA_HIP_ERR_INTERNAL, "scheduler failed") : LORA_HIP_ERR_HIP; }
-        h->pass_open = true;
-        sp.inflight = true; sp.fl_off = sp.tailcap - sp.tail_len; sp.fl_len = len;
-        sp.cur ^= 1; sp.fill = 0; sp.tail_len = 0;
-        sp.have_first = false;
-        sp.passes++;
-    }
-    // (shorter than one work() call of the reference, :91: keep filling the same chunk)
-    return LORA_HIP_OK;
 }
 
 lora_hip_status lora_hip_work(lora_hip_decoder_t *h, const float *iq, size_t n_items, size_t *consumed)
 {
     if (!h || (!iq && n_items)) return LORA_HIP_ERR_ARG;
-    if (h->pass_open && !h->sp.inflight) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_work: a lora_hip_decode_device_begin pass is open on this handle");
-    lora_hip_status s = stream_pipe_init(h);
-    if (s != LORA_HIP_OK) return s;
+    ChunkPipe &p = h->pipe;
+    if (h->pass_open && !p.inflight) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_work: a lora_hip_decode_device_begin pass is open on this handle");
     HIP_TRY(h, hipSetDevice(h->device));
-    auto &sp = h->sp;
+    lora_hip_status s = pipe_open(h);
+    if (s != LORA_HIP_OK) return s;
+    s = pipe_collect_if_done(h);
+    if (s != LORA_HIP_OK) return s;
+    ChunkPipe::Chan &c = p.ch[0];
+    auto &f = h->feed;
     const float2 *src = reinterpret_cast<const float2 *>(iq);
     size_t left = n_items;
     bool direct_pending = false;
-    // a pass whose kernel has finished is collected now - its frames are published by this call, not a chunk later
-    if (sp.inflight && h->pending.open && hipEventQuery(h->ev_done) == hipSuccess) {
-        s = stream_collect(h);
-        if (s != LORA_HIP_OK) return s;
-    }
-    (void)hipGetLastError(); // (hipErrorNotReady of the query)
     const bool direct = n_items != 0 && stream_host_pinned(h, iq, n_items * sizeof(float2)); // (the whole call's range, once)
     while (left) {
-        if (sp.fill == h->batch_items) { // (a chunk that could not be launched yet because the stream was shorter than 2 sps)
-            s = stream_rotate(h);
+        if (c.fill == p.batch) { // (a chunk that could not be launched yet because the stream was shorter than 2 sps)
+            s = pipe_rotate(h, false);
             if (s != LORA_HIP_OK) return s;
-            if (sp.fill == h->batch_items) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "batch_items is smaller than two symbols");
+            if (c.fill == p.batch) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "batch_items is smaller than two symbols");
         }
-        const size_t m = std::min(left, h->batch_items - sp.fill);
-        float2 *dst = sp.dbuf[sp.cur].p + sp.tailcap + sp.fill;
+        const size_t m = std::min(left, p.batch - c.fill);
+        float2 *dst = p.row(0);
         if (direct) {
-            HIP_TRY(h, hipMemcpyAsync(dst, src, m * sizeof(float2), hipMemcpyHostToDevice, sp.copy_st));
+            HIP_TRY(h, hipMemcpyAsync(dst, src, m * sizeof(float2), hipMemcpyHostToDevice, p.copy_st));
             direct_pending = true;
-            sp.bytes_direct += m * sizeof(float2);
         } else { // through a pinned bounce buffer, in pieces, two in flight
             size_t done = 0;
-            const size_t piece = std::max<size_t>(h->batch_items / 4u, 16384u);
+            const size_t piece = std::max<size_t>(p.batch / 4u, 16384u);
             while (done < m) {
                 const size_t q = std::min(piece, m - done);
-                const int k = sp.stage_i;
-                if (sp.stage_busy[k]) { HIP_TRY(h, hipEventSynchronize(sp.stage_ev[k])); sp.stage_busy[k] = false; }
-                HIP_TRY(h, sp.stage[k].reserve(piece));
-                std::memcpy(sp.stage[k].p, src + done, q * sizeof(float2));
-                HIP_TRY(h, hipMemcpyAsync(dst + done, sp.stage[k].p, q * sizeof(float2), hipMemcpyHostToDevice, sp.copy_st));
-                HIP_TRY(h, hipEventRecord(sp.stage_ev[k], sp.copy_st));
-                sp.stage_busy[k] = true;
-                sp.stage_i ^= 1;
+                const int k = f.stage_i;
+                if (!f.stage_ev[k]) HIP_TRY(h, hipEventCreateWithFlags(&f.stage_ev[k], hipEventDisableTiming));
+                if (f.stage_busy[k]) { HIP_TRY(h, hipEventSynchronize(f.stage_ev[k])); f.stage_busy[k] = false; }
+                HIP_TRY(h, f.stage[k].reserve(piece));
+                std::memcpy(f.stage[k].p, src + done, q * sizeof(float2));
+                HIP_TRY(h, hipMemcpyAsync(dst + done, f.stage[k].p, q * sizeof(float2), hipMemcpyHostToDevice, p.copy_st));
+                HIP_TRY(h, hipEventRecord(f.stage_ev[k], p.copy_st));
+                f.stage_busy[k] = true;
+                f.stage_i ^= 1;
                 done += q;
             }
-            sp.bytes_staged += m * sizeof(float2);
         }
-        if (!sp.have_first) { sp.have_first = true; sp.t_first = std::chrono::steady_clock::now(); }
-        sp.fill += m; src += m; left -= m;
-        if (sp.fill == h->batch_items) {
-            s = stream_rotate(h);
+        if (!p.have_first) { p.have_first = true; p.t_first = std::chrono::steady_clock::now(); }
+        c.fill += m; src += m; left -= m;
+        if (c.fill == p.batch) {
+            s = pipe_rotate(h, false);
             if (s != LORA_HIP_OK) return s;
         }
     }
     // the caller may reuse its buffer as soon as we return (the scheduler's contract): the DMA out of it must be done
-    if (direct_pending) HIP_TRY(h, hipStreamSynchronize(sp.copy_st));
-    // latency bound: the oldest sample not yet handed to a pass has waited long enough (and a pass could run at all, :91)
-    if (sp.max_latency_ms > 0.0f && sp.have_first && sp.fill != 0 && sp.tail_len + sp.fill >= 2u * (size_t)h->P.sps &&
-        std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - sp.t_first).count() >= sp.max_latency_ms) {
-        const uint64_t before = sp.passes;
-        s = stream_rotate(h);
+    if (direct_pending) HIP_TRY(h, hipStreamSynchronize(p.copy_st));
+    if (pipe_latency_due(h)) {
+        s = pipe_rotate(h, true);
         if (s != LORA_HIP_OK) return s;
-        sp.passes_by_latency += sp.passes - before;
     }
     if (consumed) *consumed = n_items;
     return LORA_HIP_OK;
@@ -1390,68 +1434,120 @@ lora_hip_status lora_hip_work(lora_hip_decoder_t *h, const float *iq, size_t n_i
 lora_hip_status lora_hip_set_stream_latency(lora_hip_decoder_t *h, float max_latency_ms)
 {
     if (!h || !(max_latency_ms >= 0.0f)) return LORA_HIP_ERR_ARG;
-    h->sp.max_latency_ms = max_latency_ms;
+    h->pipe.max_latency_ms = max_latency_ms;
     return LORA_HIP_OK;
 }
 
 lora_hip_status lora_hip_stream_info(const lora_hip_decoder_t *h, lora_hip_stream_info_t *out)
 {
     if (!h || !out) return LORA_HIP_ERR_ARG;
-    out->batch_items = h->batch_items;
-    out->buffered_items = h->sp.tail_len + h->sp.fill;
-    out->passes = h->sp.passes; out->passes_by_latency = h->sp.passes_by_latency;
-    out->consumed_base = h->host_base;
-    out->max_latency_ms = h->sp.max_latency_ms;
-    out->pass_in_flight = h->sp.inflight ? 1u : 0u;
+    const ChunkPipe &p = h->pipe;
+    out->batch_items = p.batch;
+    out->buffered_items = p.ch[0].tail_len + p.ch[0].fill;
+    out->passes = p.passes; out->passes_by_latency = p.passes_by_latency;
+    out->consumed_base = p.ch[0].host_base;
+    out->max_latency_ms = p.max_latency_ms;
+    out->pass_in_flight = p.inflight ? 1u : 0u;
     return LORA_HIP_OK;
 }
 
 lora_hip_status lora_hip_flush(lora_hip_decoder_t *h)
 {
     if (!h) return LORA_HIP_ERR_ARG;
-    if (!h->sp.copy_st) return LORA_HIP_OK; // nothing was ever fed
+    if (!h->pipe.copy_st) return LORA_HIP_OK; // nothing was ever fed
     HIP_TRY(h, hipSetDevice(h->device));
-    lora_hip_status s = stream_rotate(h); // launches what is buffered (collecting the pass before it)
+    lora_hip_status s = pipe_rotate(h, false); // launches what is buffered (collecting the pass before it)
     if (s != LORA_HIP_OK) return s;
-    s = stream_collect(h);                // ... and collects that one as well; its tail waits in front of the next chunk
+    s = pipe_collect(h);                       // ... and collects that one as well; its tail waits in front of the next chunk
     if (s != LORA_HIP_OK) return s;
-    HIP_TRY(h, hipStreamSynchronize(h->sp.comp_st));
+    HIP_TRY(h, hipStreamSynchronize(h->pipe.comp_st));
     return LORA_HIP_OK;
 }
 
+} // extern "C"
+
 // ---- lora_hip_mux: many channels, one pass (the gateway flowgraph; see include/lora_hip.h) ------------------------------
-// Device layout: two buffers of n_channels regions [ tail area (tailcap items, right-aligned) | chunk (batch items) ]; the
-// pass over buffer b decodes n_channels streams (region c: the last tail_len[c] items of the tail area + the chunk's fill[c]
-// items), while the channels go on filling buffer b ^ 1.  What a pass did not consume of a channel (an unfinished packet) is
-// copied in front of that channel's next chunk when the pass is collected.  Decoder state crossing passes (d_phdr.cr, power
-// queue, absolute position) is carried per channel exactly as lora_hip_work carries it for its one stream.
+// A decoder handle whose pipeline has n_channels channels, each carried exactly as lora_hip_work carries its one stream, fed from
+// host memory (lora_hip_mux_work) or by a writer on the device (lora_mux_dev.h).  A pass is launched when every channel's chunk is
+// full; what a channel delivers beyond its chunk waits in host memory and refills its next chunks.
+namespace {
+struct MuxSurplus {
+    std::vector<float2> ahead; // what the channel delivered beyond its chunk (it runs chunks ahead of the slowest one)
+    size_t ahead_off = 0;      // items of `ahead` already uploaded (a read offset: the front is erased only once it is more than half of the vector)
+    size_t left() const { return ahead.size() - ahead_off; }
+};
+} // namespace
+
 struct lora_hip_mux {
-    lora_hip_decoder *h = nullptr;   // tables, kernels, scheduler, frame queue
-    uint32_t n = 0;
-    size_t batch = 0, tailcap = 0, region = 0;
-    DevBuf<float2> dbuf[2];
-    int cur = 0;
-    struct Chan { size_t fill = 0, tail_len = 0; uint32_t cr = 0; PwrState pwr; int64_t host_base = 0; std::vector<float2> ahead; size_t fl_off = 0, fl_len = 0; bool in_pass = false;
-                  size_t ahead_off = 0; // items of `ahead` already uploaded (a read offset: the front is erased only once it is more than half of the vector)
-                  size_t ahead_left() const { return ahead.size() - ahead_off; } };
-    std::vector<Chan> ch;
-    hipStream_t copy_st = nullptr, comp_st = nullptr;
-    hipEvent_t up_ev = nullptr, tail_ev = nullptr;
-    hipEvent_t fed_ev = nullptr;     // the device-fed path (lora_mux_dev.h): recorded on copy_st for a writer of the chunk area to wait on
-    bool inflight = false;
-    float max_latency_ms = 50.0f;
-    size_t max_ahead = 0;            // surplus of one channel (items in host memory) at which a pass goes without waiting for the others
-    std::chrono::steady_clock::time_point t_first;
-    bool have_first = false;
-    uint64_t passes = 0, passes_by_latency = 0;
-    std::string err;
+    lora_hip_decoder *h = nullptr; // tables, kernels, scheduler, frame queue, pipeline
+    std::vector<MuxSurplus> ch;
+    size_t max_ahead = 0;          // surplus of one channel at which a pass goes without waiting for the others
+    hipEvent_t fed_ev = nullptr;   // the device-fed path: recorded on copy_st for a writer of the chunk area to wait on
 };
 
-#define MUX_TRY(m, expr)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess) { (m)->err = std::string(#expr) + ": " + hipGetErrorString(e__); return LORA_HIP_ERR_HIP; } \
-    } while (0)
+namespace {
+
+lora_hip_status mux_upload(lora_hip_mux *m, uint32_t c, const float2 *src, size_t n)
+{
+    lora_hip_decoder *h = m->h;
+    HIP_TRY(h, hipMemcpyAsync(h->pipe.row(c), src, n * sizeof(float2), hipMemcpyHostToDevice, h->pipe.copy_st));
+    h->pipe.ch[c].fill += n;
+    return LORA_HIP_OK;
+}
+
+// a rotation (pipe_rotate); if it launched a pass, the new chunks are refilled from the surplus
+lora_hip_status mux_pass(lora_hip_mux *m, bool by_latency)
+{
+    lora_hip_decoder *h = m->h;
+    ChunkPipe &p = h->pipe;
+    const uint64_t before = p.passes;
+    lora_hip_status s = pipe_rotate(h, by_latency);
+    if (s != LORA_HIP_OK || p.passes == before) return s;
+    // every upload is queued first, the copy stream is waited for ONCE, and only then do the host vectors change
+    bool any_up = false;
+    for (uint32_t c = 0; c < m->ch.size(); c++) {
+        MuxSurplus &S = m->ch[c];
+        if (S.left() == 0) continue;
+        s = mux_upload(m, c, S.ahead.data() + S.ahead_off, std::min(S.left(), p.batch));
+        if (s != LORA_HIP_OK) return s;
+        any_up = true;
+    }
+    if (!any_up) return LORA_HIP_OK;
+    HIP_TRY(h, hipStreamSynchronize(p.copy_st)); // (the vectors are about to change)
+    for (uint32_t c = 0; c < m->ch.size(); c++) {
+        MuxSurplus &S = m->ch[c];
+        S.ahead_off += p.ch[c].fill; // (the pass emptied every chunk: what one holds now came from the surplus)
+        if (S.ahead_off == S.ahead.size()) { S.ahead.clear(); S.ahead_off = 0; }
+        else if (S.ahead_off > S.ahead.size() / 2) { S.ahead.erase(S.ahead.begin(), S.ahead.begin() + (ptrdiff_t)S.ahead_off); S.ahead_off = 0; }
+    }
+    if (!p.have_first) { p.have_first = true; p.t_first = std::chrono::steady_clock::now(); }
+    return LORA_HIP_OK;
+}
+
+// after new samples (lora_hip_mux_work and the device-fed path): a pass while every channel's chunk is full (again, while the surplus
+// refills whole chunks) - or while one channel's surplus has reached max_ahead (a silent or stalled neighbour must not let it grow
+// without bound when the latency bound is off: the others then go into the pass with what they hold) - then the latency bound
+lora_hip_status mux_pass_loop(lora_hip_mux *m)
+{
+    ChunkPipe &p = m->h->pipe;
+    for (;;) {
+        bool all_full = true, far_ahead = false;
+        for (size_t c = 0; c < p.ch.size(); c++) {
+            all_full = all_full && p.ch[c].fill == p.batch;
+            far_ahead = far_ahead || (p.ch[c].fill == p.batch && m->ch[c].left() >= m->max_ahead);
+        }
+        if (!all_full && !far_ahead) break;
+        const uint64_t before = p.passes;
+        const lora_hip_status s = mux_pass(m, false);
+        if (s != LORA_HIP_OK) return s;
+        if (p.passes == before) break; // (nothing could be launched)
+    }
+    return pipe_latency_due(m->h) ? mux_pass(m, true) : LORA_HIP_OK;
+}
+
+} // namespace
+
+extern "C" {
 
 lora_hip_status lora_hip_mux_create(const lora_hip_config_t *cfg, uint32_t n_channels, lora_hip_mux_t **out)
 {
@@ -1462,18 +1558,12 @@ lora_hip_status lora_hip_mux_create(const lora_hip_config_t *cfg, uint32_t n_cha
     if (s != LORA_HIP_OK) return s;
     lora_hip_mux *m = new (std::nothrow) lora_hip_mux();
     if (!m) { lora_hip_destroy(h); return LORA_HIP_ERR_NOMEM; }
-    m->h = h; m->n = n_channels;
-    m->batch = cfg->batch_items ? cfg->batch_items : std::max<size_t>(1u << 18, 64ull * h->P.sps); // (n channels share a pass: smaller chunks than one stream's)
-    m->tailcap = std::max<size_t>(m->batch, 4u * (size_t)h->P.sps);
-    m->region = m->tailcap + m->batch;
-    m->max_ahead = std::max<size_t>(8u * m->batch, (size_t)1 << 22);
+    m->h = h;
     m->ch.resize(n_channels);
-    for (auto &c : m->ch) c.cr = h->P.ctor_cr;
-    bool ok = hipSetDevice(h->device) == hipSuccess && hipStreamCreateWithFlags(&m->copy_st, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&m->comp_st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&m->up_ev, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&m->tail_ev, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; ok && i < 2; i++) ok = m->dbuf[i].reserve((size_t)n_channels * m->region) == hipSuccess;
-    if (!ok) { lora_hip_mux_destroy(m); return LORA_HIP_ERR_HIP; }
+    pipe_init(h, n_channels, cfg->batch_items ? cfg->batch_items : std::max<size_t>(1u << 18, 64ull * h->P.sps)); // (n channels share a pass: smaller chunks than one stream's)
+    (void)lora_hip_mux_set_max_ahead(m, 0);
+    s = pipe_open(h); // (lora_hip_create has made h->device current)
+    if (s != LORA_HIP_OK) { lora_hip_mux_destroy(m); return s; }
     *out = m;
     return LORA_HIP_OK;
 }
@@ -1481,290 +1571,68 @@ lora_hip_status lora_hip_mux_create(const lora_hip_config_t *cfg, uint32_t n_cha
 void lora_hip_mux_destroy(lora_hip_mux_t *m)
 {
     if (!m) return;
-    if (m->h) (void)hipSetDevice(m->h->device);
-    if (m->copy_st) { (void)hipStreamSynchronize(m->copy_st); }
-    if (m->comp_st) { (void)hipStreamSynchronize(m->comp_st); }
-    for (int i = 0; i < 2; i++) m->dbuf[i].release();
-    if (m->up_ev) (void)hipEventDestroy(m->up_ev);
-    if (m->tail_ev) (void)hipEventDestroy(m->tail_ev);
+    lora_hip_destroy(m->h); // (waits for the pipeline's streams)
     if (m->fed_ev) (void)hipEventDestroy(m->fed_ev);
-    if (m->copy_st) (void)hipStreamDestroy(m->copy_st);
-    if (m->comp_st) (void)hipStreamDestroy(m->comp_st);
-    if (m->h) { m->h->pass_open = false; lora_hip_destroy(m->h); }
     delete m;
 }
 
-const char *lora_hip_mux_last_error(const lora_hip_mux_t *m) { return m ? (m->err.empty() ? m->h->err.c_str() : m->err.c_str()) : g_create_err.c_str(); }
-
-// collects the pass in flight: per channel its decoder state, its frames (published through the handle's queue) and its tail
-static lora_hip_status mux_collect(lora_hip_mux *m)
-{
-    if (!m->inflight) return LORA_HIP_OK;
-    lora_hip_decoder *h = m->h;
-    m->inflight = false;
-    h->pass_open = false;
-    h->err.clear();
-    DeviceEnv env{h, h->pass_iq, h->pass_st};
-    const int rc = lora_hip::decode_end(env, h->pass_streams, h->pass);
-    if (rc != 0) { h->pending.open = false; m->err = h->err.empty() ? "scheduler failed" : h->err; return LORA_HIP_ERR_INTERNAL; }
-    const int prev = m->cur ^ 1; // the buffer the pass ran on
-    bool any_tail = false;
-    for (const StreamDesc &sd : h->pass_streams) {
-        lora_hip_mux::Chan &c = m->ch[sd.id];
-        c.in_pass = false;
-        c.cr = sd.cr_out; c.pwr = sd.pwr;
-        const size_t keep_from = (size_t)std::min<int64_t>(std::max<int64_t>(sd.final_pos, 0), (int64_t)c.fl_len);
-        const size_t tail = c.fl_len - keep_from;
-        c.host_base += (int64_t)keep_from;
-        if (tail > m->tailcap) { // a packet longer than the tail area: grow both buffers, every region keeps its chunk and the right end of its tail area
-            const size_t ncap = std::max(2u * m->tailcap, tail + (size_t)h->P.sps), nregion = ncap + m->batch;
-            MUX_TRY(m, hipStreamSynchronize(m->copy_st));
-            MUX_TRY(m, hipStreamSynchronize(m->comp_st));
-            for (int i = 0; i < 2; i++) {
-                DevBuf<float2> nb;
-                MUX_TRY(m, nb.reserve((size_t)m->n * nregion));
-                for (uint32_t q = 0; q < m->n; q++)
-                    MUX_TRY(m, hipMemcpyAsync(nb.p + (size_t)q * nregion + (ncap - m->tailcap), m->dbuf[i].p + (size_t)q * m->region, m->region * sizeof(float2), hipMemcpyDeviceToDevice, m->comp_st));
-                MUX_TRY(m, hipStreamSynchronize(m->comp_st));
-                std::swap(m->dbuf[i], nb);
-                nb.release();
-            }
-            for (auto &cc : m->ch) cc.fl_off = (cc.fl_off / m->region) * nregion + (cc.fl_off % m->region) + (ncap - m->tailcap);
-            m->tailcap = ncap; m->region = nregion;
-        }
-        if (tail) {
-            MUX_TRY(m, hipMemcpyAsync(m->dbuf[m->cur].p + (size_t)sd.id * m->region + m->tailcap - tail, m->dbuf[prev].p + c.fl_off + keep_from, tail * sizeof(float2),
-                                      hipMemcpyDeviceToDevice, m->comp_st));
-            any_tail = true;
-        }
-        c.tail_len = tail;
-    }
-    if (any_tail) { // the sources sit in chunk areas the next uploads overwrite: they wait for these copies
-        MUX_TRY(m, hipEventRecord(m->tail_ev, m->comp_st));
-        MUX_TRY(m, hipStreamWaitEvent(m->copy_st, m->tail_ev, 0));
-    }
-    return LORA_HIP_OK;
-}
-
-static lora_hip_status mux_upload(lora_hip_mux *m, uint32_t c, const float2 *src, size_t n)
-{
-    lora_hip_mux::Chan &C = m->ch[c];
-    MUX_TRY(m, hipMemcpyAsync(m->dbuf[m->cur].p + (size_t)c * m->region + m->tailcap + C.fill, src, n * sizeof(float2), hipMemcpyHostToDevice, m->copy_st));
-    C.fill += n;
-    return LORA_HIP_OK;
-}
-
-static lora_hip_status mux_pass_loop(lora_hip_mux *m);
-
-// launches a pass over what every channel holds (collecting the pass before it), then refills the new chunk from the surplus
-static lora_hip_status mux_rotate(lora_hip_mux *m, bool by_latency)
-{
-    lora_hip_decoder *h = m->h;
-    MUX_TRY(m, hipEventRecord(m->up_ev, m->copy_st));
-    lora_hip_status s = mux_collect(m);
-    if (s != LORA_HIP_OK) return s;
-    std::vector<StreamDesc> &sds = h->pass_streams;
-    sds.clear();
-    uint64_t items = 0;
-    for (uint32_t c = 0; c < m->n; c++) {
-        lora_hip_mux::Chan &C = m->ch[c];
-        const size_t len = C.tail_len + C.fill;
-        if (len < 2u * (size_t)h->P.sps) continue; // (:91: not a work() call's worth yet; it stays where it is)
-        StreamDesc sd{};
-        sd.off = (uint64_t)c * m->region + m->tailcap - C.tail_len; sd.len = len; sd.id = c;
-        sd.cr_in = C.cr; sd.pwr = C.pwr; sd.abs_base = C.host_base;
-        sds.push_back(sd);
-        C.fl_off = (size_t)sd.off; C.fl_len = len; C.in_pass = true;
-        items += len;
-    }
-    if (sds.empty()) return LORA_HIP_OK;
-    MUX_TRY(m, hipStreamWaitEvent(m->comp_st, m->up_ev, 0));
-    h->timing = lora_hip_timing_t{};
-    h->timing.items = items;
-    h->pass_iq = m->dbuf[m->cur].p; h->pass_st = m->comp_st;
-    h->err.clear();
-    DeviceEnv env{h, h->pass_iq, h->pass_st};
-    if (lora_hip::decode_begin(env, sds, h->pass) != 0) { h->pending.open = false; m->err = h->err.empty() ? "scheduler failed" : h->err; return LORA_HIP_ERR_INTERNAL; }
-    h->pass_open = true;
-    m->inflight = true;
-    m->passes++; m->passes_by_latency += by_latency ? 1u : 0u;
-    const int old = m->cur;
-    m->cur ^= 1;
-    m->have_first = false;
-    for (uint32_t c = 0; c < m->n; c++) {
-        lora_hip_mux::Chan &C = m->ch[c];
-        if (!C.in_pass) { // too short to be decoded yet: its samples move along to the new buffer
-            const size_t len = C.tail_len + C.fill;
-            if (len) MUX_TRY(m, hipMemcpyAsync(m->dbuf[m->cur].p + (size_t)c * m->region + m->tailcap - len, m->dbuf[old].p + (size_t)c * m->region + m->tailcap - C.tail_len, len * sizeof(float2),
-                                               hipMemcpyDeviceToDevice, m->copy_st));
-            C.tail_len = len; C.fill = 0;
-        } else { C.fill = 0; C.tail_len = 0; }
-    }
-    // what the channels delivered beyond their chunks: every upload is queued first, the copy stream is waited for ONCE, and only then do the
-    // host vectors change (one synchronisation and one front erase per channel and rotation used to serialise n_channels waits and ~32 MB memmoves)
-    std::vector<size_t> took(m->n, 0);
-    bool any_up = false;
-    for (uint32_t c = 0; c < m->n; c++) {
-        lora_hip_mux::Chan &C = m->ch[c];
-        if (C.ahead_left() == 0) continue;
-        took[c] = std::min(C.ahead_left(), m->batch);
-        s = mux_upload(m, c, C.ahead.data() + C.ahead_off, took[c]);
-        if (s != LORA_HIP_OK) return s;
-        any_up = true;
-    }
-    if (any_up) {
-        MUX_TRY(m, hipStreamSynchronize(m->copy_st)); // (the vectors are about to change)
-        for (uint32_t c = 0; c < m->n; c++)
-            if (took[c]) {
-                lora_hip_mux::Chan &C = m->ch[c];
-                C.ahead_off += took[c];
-                if (C.ahead_off == C.ahead.size()) { C.ahead.clear(); C.ahead_off = 0; }
-                else if (C.ahead_off > C.ahead.size() / 2) { C.ahead.erase(C.ahead.begin(), C.ahead.begin() + (ptrdiff_t)C.ahead_off); C.ahead_off = 0; }
-            }
-        if (!m->have_first) { m->have_first = true; m->t_first = std::chrono::steady_clock::now(); }
-    }
-    return LORA_HIP_OK;
-}
+const char *lora_hip_mux_last_error(const lora_hip_mux_t *m) { return m ? m->h->err.c_str() : g_create_err.c_str(); }
 
 lora_hip_status lora_hip_mux_work(lora_hip_mux_t *m, uint32_t channel, const float *iq, size_t n_items)
 {
-    if (!m || channel >= m->n || (!iq && n_items)) return LORA_HIP_ERR_ARG;
+    if (!m || channel >= m->ch.size() || (!iq && n_items)) return LORA_HIP_ERR_ARG;
     lora_hip_decoder *h = m->h;
-    MUX_TRY(m, hipSetDevice(h->device));
-    m->err.clear();
-    lora_hip_status s;
-    if (m->inflight && h->pending.open && hipEventQuery(h->ev_done) == hipSuccess) { // finished: publish now
-        s = mux_collect(m);
-        if (s != LORA_HIP_OK) return s;
-    }
-    (void)hipGetLastError();
-    lora_hip_mux::Chan &C = m->ch[channel];
+    ChunkPipe &p = h->pipe;
+    HIP_TRY(h, hipSetDevice(h->device));
+    lora_hip_status s = pipe_collect_if_done(h);
+    if (s != LORA_HIP_OK) return s;
+    MuxSurplus &S = m->ch[channel];
     const float2 *src = reinterpret_cast<const float2 *>(iq);
     size_t left = n_items;
-    if (left && C.ahead_left() == 0) {
-        const size_t k = std::min(left, m->batch - C.fill);
+    if (left && S.left() == 0) {
+        const size_t k = std::min(left, p.batch - p.ch[channel].fill);
         if (k) {
             s = mux_upload(m, channel, src, k);
             if (s != LORA_HIP_OK) return s;
-            if (!m->have_first) { m->have_first = true; m->t_first = std::chrono::steady_clock::now(); }
+            if (!p.have_first) { p.have_first = true; p.t_first = std::chrono::steady_clock::now(); }
             src += k; left -= k;
         }
     }
-    if (left) C.ahead.insert(C.ahead.end(), src, src + left); // this channel is a chunk ahead of the slowest one
-    MUX_TRY(m, hipStreamSynchronize(m->copy_st)); // the caller may reuse its buffer
+    if (left) S.ahead.insert(S.ahead.end(), src, src + left); // this channel is a chunk ahead of the slowest one
+    HIP_TRY(h, hipStreamSynchronize(p.copy_st)); // the caller may reuse its buffer
     return mux_pass_loop(m);
 }
-
-// after new samples: a pass while every chunk is full, and the latency bound (lora_hip_mux_work and the device-fed path)
-static lora_hip_status mux_pass_loop(lora_hip_mux *m)
-{
-    lora_hip_decoder *h = m->h;
-    lora_hip_status s;
-    for (;;) { // a pass when every channel's chunk is full (again, while the surplus refills whole chunks) - or when one channel's surplus
-               // has reached max_ahead (a silent or stalled neighbour must not let it grow without bound when the latency bound is off:
-               // the others then go into the pass with what they hold)
-        bool all_full = true, far_ahead = false;
-        for (const auto &c : m->ch) { all_full = all_full && c.fill == m->batch; far_ahead = far_ahead || (c.fill == m->batch && c.ahead_left() >= m->max_ahead); }
-        if (!all_full && !far_ahead) break;
-        const uint64_t before = m->passes;
-        s = mux_rotate(m, false);
-        if (s != LORA_HIP_OK) return s;
-        if (m->passes == before) break; // (nothing could be launched)
-    }
-    if (m->max_latency_ms > 0.0f && m->have_first &&
-        std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - m->t_first).count() >= m->max_latency_ms) {
-        bool any = false;
-        for (const auto &c : m->ch) any = any || (c.fill != 0 && c.tail_len + c.fill >= 2u * (size_t)h->P.sps);
-        if (any) { s = mux_rotate(m, true); if (s != LORA_HIP_OK) return s; }
-    }
-    return LORA_HIP_OK;
-}
-
-} // extern "C"
-
-namespace lora_mux_dev {
-
-lora_hip_status collect_if_done(lora_hip_mux *m)
-{
-    m->err.clear();
-    lora_hip_status s = LORA_HIP_OK;
-    if (m->inflight && m->h->pending.open && hipEventQuery(m->h->ev_done) == hipSuccess) s = mux_collect(m);
-    (void)hipGetLastError();
-    return s;
-}
-
-size_t batch(const lora_hip_mux *m) { return m->batch; }
-
-size_t room(const lora_hip_mux *m)
-{
-    size_t r = m->batch;
-    for (const auto &c : m->ch) r = std::min(r, m->batch - c.fill);
-    return r;
-}
-
-void rows(const lora_hip_mux *m, void **out)
-{
-    for (uint32_t c = 0; c < m->n; c++) out[c] = m->dbuf[m->cur].p + (size_t)c * m->region + m->tailcap + m->ch[c].fill;
-}
-
-lora_hip_status before_write(lora_hip_mux *m, hipStream_t st)
-{
-    // copy_st holds the moves of channels too short for a pass (they read the chunk area of what becomes the current buffer
-    // one rotation later) and already waits for the tail copies of the last collect (tail_ev, same reason): st waits for both
-    if (!m->fed_ev) MUX_TRY(m, hipEventCreateWithFlags(&m->fed_ev, hipEventDisableTiming));
-    MUX_TRY(m, hipEventRecord(m->fed_ev, m->copy_st));
-    MUX_TRY(m, hipStreamWaitEvent(st, m->fed_ev, 0));
-    return LORA_HIP_OK;
-}
-
-lora_hip_status commit(lora_hip_mux *m, size_t n, hipEvent_t written)
-{
-    if (n > room(m)) { m->err = "device-fed commit beyond the chunk"; return LORA_HIP_ERR_INTERNAL; }
-    MUX_TRY(m, hipStreamWaitEvent(m->copy_st, written, 0)); // the next pass waits for copy_st (up_ev), hence for the writer
-    for (auto &c : m->ch) c.fill += n;
-    if (n && !m->have_first) { m->have_first = true; m->t_first = std::chrono::steady_clock::now(); }
-    return mux_pass_loop(m);
-}
-
-} // namespace lora_mux_dev
-
-extern "C" {
 
 lora_hip_status lora_hip_mux_flush(lora_hip_mux_t *m)
 {
     if (!m) return LORA_HIP_ERR_ARG;
-    MUX_TRY(m, hipSetDevice(m->h->device));
+    lora_hip_decoder *h = m->h;
+    HIP_TRY(h, hipSetDevice(h->device));
     lora_hip_status s;
     for (int guard = 0; guard < 1 << 20; guard++) { // until nothing waits in host memory either
-        const uint64_t before = m->passes;
-        s = mux_rotate(m, false);
+        const uint64_t before = h->pipe.passes;
+        s = mux_pass(m, false);
         if (s != LORA_HIP_OK) return s;
         bool more = false;
-        for (const auto &c : m->ch) more = more || c.ahead_left() != 0;
-        if (!more && m->passes == before) break; // nothing launched and nothing left to upload: what remains is shorter than a work() call (:91)
-        if (!more) { // the last uploads are in: one more pass takes them
-            bool any = false;
-            for (const auto &c : m->ch) any = any || (c.fill != 0 && c.tail_len + c.fill >= 2u * (size_t)m->h->P.sps);
-            if (!any) break;
-        }
+        for (const auto &c : m->ch) more = more || c.left() != 0;
+        if (!more && h->pipe.passes == before) break; // nothing launched and nothing left to upload: what remains is shorter than a work() call (:91)
+        if (!more && !pipe_launchable(h)) break;      // (the last uploads are in: one more pass takes them, if they are enough for one)
     }
-    s = mux_collect(m);
+    s = pipe_collect(h);
     if (s != LORA_HIP_OK) return s;
-    MUX_TRY(m, hipStreamSynchronize(m->comp_st));
+    HIP_TRY(h, hipStreamSynchronize(h->pipe.comp_st));
     return LORA_HIP_OK;
 }
 
 lora_hip_status lora_hip_mux_set_latency(lora_hip_mux_t *m, float max_latency_ms)
 {
-    if (!m || !(max_latency_ms >= 0.0f)) return LORA_HIP_ERR_ARG;
-    m->max_latency_ms = max_latency_ms;
-    return LORA_HIP_OK;
+    return m ? lora_hip_set_stream_latency(m->h, max_latency_ms) : LORA_HIP_ERR_ARG;
 }
 
 lora_hip_status lora_hip_mux_set_max_ahead(lora_hip_mux_t *m, size_t max_ahead_items)
 {
     if (!m) return LORA_HIP_ERR_ARG;
-    m->max_ahead = max_ahead_items ? max_ahead_items : std::max<size_t>(8u * m->batch, (size_t)1 << 22);
+    m->max_ahead = max_ahead_items ? max_ahead_items : std::max<size_t>(8u * m->h->pipe.batch, (size_t)1 << 22);
     return LORA_HIP_OK;
 }
 
@@ -1778,10 +1646,57 @@ lora_hip_status lora_hip_mux_poll_frame(lora_hip_mux_t *m, uint8_t *buf, size_t 
 lora_hip_status lora_hip_mux_passes(const lora_hip_mux_t *m, uint64_t *passes, uint64_t *passes_by_latency)
 {
     if (!m) return LORA_HIP_ERR_ARG;
-    if (passes) *passes = m->passes;
-    if (passes_by_latency) *passes_by_latency = m->passes_by_latency;
+    if (passes) *passes = m->h->pipe.passes;
+    if (passes_by_latency) *passes_by_latency = m->h->pipe.passes_by_latency;
     return LORA_HIP_OK;
 }
+
+} // extern "C"
+
+namespace lora_mux_dev {
+
+lora_hip_status collect_if_done(lora_hip_mux *m) { return pipe_collect_if_done(m->h); }
+
+size_t batch(const lora_hip_mux *m) { return m->h->pipe.batch; }
+
+size_t room(const lora_hip_mux *m)
+{
+    const ChunkPipe &p = m->h->pipe;
+    size_t r = p.batch;
+    for (const ChunkPipe::Chan &c : p.ch) r = std::min(r, p.batch - c.fill);
+    return r;
+}
+
+void rows(const lora_hip_mux *m, void **out)
+{
+    for (size_t c = 0; c < m->ch.size(); c++) out[c] = m->h->pipe.row(c);
+}
+
+lora_hip_status before_write(lora_hip_mux *m, hipStream_t st)
+{
+    // copy_st holds the moves of channels too short for a pass (they read the chunk area of what becomes the current buffer
+    // one rotation later) and already waits for the tail copies of the last collect (tail_ev, same reason): st waits for both
+    lora_hip_decoder *h = m->h;
+    if (!m->fed_ev) HIP_TRY(h, hipEventCreateWithFlags(&m->fed_ev, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(m->fed_ev, h->pipe.copy_st));
+    HIP_TRY(h, hipStreamWaitEvent(st, m->fed_ev, 0));
+    return LORA_HIP_OK;
+}
+
+lora_hip_status commit(lora_hip_mux *m, size_t n, hipEvent_t written)
+{
+    lora_hip_decoder *h = m->h;
+    ChunkPipe &p = h->pipe;
+    if (n > room(m)) return fail(h, LORA_HIP_ERR_INTERNAL, "device-fed commit beyond the chunk");
+    HIP_TRY(h, hipStreamWaitEvent(p.copy_st, written, 0)); // the next pass waits for copy_st (up_ev), hence for the writer
+    for (ChunkPipe::Chan &c : p.ch) c.fill += n;
+    if (n && !p.have_first) { p.have_first = true; p.t_first = std::chrono::steady_clock::now(); }
+    return mux_pass_loop(m);
+}
+
+} // namespace lora_mux_dev
+
+extern "C" {
 
 size_t lora_hip_frames_available(const lora_hip_decoder_t *h) { return h ? h->frames.size() : 0; }
 

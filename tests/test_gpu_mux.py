@@ -33,7 +33,7 @@ def _batch(sf, iq):
     return out
 
 
-@pytest.mark.parametrize("sf,n", [(7, 8), (9, 5)])
+@pytest.mark.parametrize("sf,n", [(7, 8), (9, 5), (8, 1)])
 def test_mux_equals_independent_decoders(sf, n):
     from gr_lora_amd import capi
     cfg, chans = _channels(n, sf, seed=500 + sf)
