@@ -53,6 +53,12 @@ EXPORTS_GATEWAY = [
     "lora_hip_gateway_work_raw", "lora_hip_gateway_work_device_raw",
 ]
 
+EXPORTS_TX = [
+    "lora_hip_tx_encode", "lora_hip_tx_frame_items", "lora_hip_tx_create", "lora_hip_tx_destroy", "lora_hip_tx_last_error", "lora_hip_tx_add_frames",
+    "lora_hip_tx_generate_device", "lora_hip_tx_generate_device_raw", "lora_hip_tx_generate", "lora_hip_tx_position", "lora_hip_tx_pending",
+    "lora_hip_tx_last_kernel_ms",
+]
+
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
 GATEWAY_MAX_DECODERS = 7      # include/lora_hip_gateway.h
 GATEWAY_STEP_OUTPUTS = 65536  # include/lora_hip_gateway.h
@@ -130,6 +136,23 @@ class GatewayStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_decoders", C.c_uint32), ("passes", C.c_uint64 * GATEWAY_MAX_DECODERS),
                 ("passes_by_latency", C.c_uint64 * GATEWAY_MAX_DECODERS), ("filterbank_calls", C.c_uint64), ("filterbank_ms", C.c_double),
                 ("items_in", C.c_uint64), ("step_outputs", C.c_uint64)]
+
+
+TX_FRAME_HDR_NIBBLES, TX_FRAME_CRC_BYTES = 1, 2  # lora_hip_tx_frame_t.flags (include/lora_hip_tx.h)
+TX_MAX_SHIFTS = 2048                             # include/lora_hip_tx.h
+
+
+class TxFrame(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("bandwidth", C.c_uint32), ("sf", C.c_uint8), ("implicit", C.c_uint8), ("cr", C.c_uint8),
+                ("crc", C.c_uint8), ("reduced_rate", C.c_uint8), ("reserved0", C.c_uint8 * 3), ("preamble_len", C.c_uint32),
+                ("sync_shifts", C.c_int32 * 2), ("flags", C.c_uint32), ("hdr_nibbles", C.c_uint8 * 2), ("crc_bytes", C.c_uint8 * 2),
+                ("start", C.c_int64), ("freq_hz", C.c_double), ("amplitude", C.c_float), ("length", C.c_uint32),
+                ("payload", C.POINTER(C.c_uint8))]
+
+
+class TxConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("samp_rate", C.c_double), ("noise_sigma", C.c_double),
+                ("seed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class LoraHipError(RuntimeError):
@@ -271,6 +294,24 @@ def load():
         L.lora_hip_filterbank_work_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.lora_hip_gateway_work_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float]
         L.lora_hip_gateway_work_device_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp]
+    if hasattr(L, "lora_hip_tx_create") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        L.lora_hip_tx_encode.argtypes = [C.POINTER(TxFrame), C.POINTER(C.c_uint16), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.lora_hip_tx_frame_items.argtypes = [C.POINTER(TxFrame), C.c_float, C.POINTER(C.c_uint64)]
+        L.lora_hip_tx_create.argtypes = [C.POINTER(TxConfig), C.POINTER(vp)]
+        L.lora_hip_tx_destroy.argtypes = [vp]
+        L.lora_hip_tx_destroy.restype = None
+        L.lora_hip_tx_last_error.argtypes = [vp]
+        L.lora_hip_tx_last_error.restype = C.c_char_p
+        L.lora_hip_tx_add_frames.argtypes = [vp, C.POINTER(TxFrame), C.c_size_t]
+        L.lora_hip_tx_generate_device.argtypes = [vp, vp, C.c_size_t, vp]
+        L.lora_hip_tx_generate_device_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_double, vp]
+        L.lora_hip_tx_generate.argtypes = [vp, vp, C.c_size_t]
+        L.lora_hip_tx_position.argtypes = [vp]
+        L.lora_hip_tx_position.restype = C.c_int64
+        L.lora_hip_tx_pending.argtypes = [vp]
+        L.lora_hip_tx_pending.restype = C.c_size_t
+        L.lora_hip_tx_last_kernel_ms.argtypes = [vp]
+        L.lora_hip_tx_last_kernel_ms.restype = C.c_float
     _lib = L
     return L
 
@@ -849,6 +890,100 @@ class Gateway:
     def close(self):
         if getattr(self, "h", None):
             self.L.lora_hip_gateway_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def tx_frame(payload, sf, cr, bandwidth, start=0, freq_hz=0.0, amplitude=1.0, crc=True, implicit=False, reduced_rate=False, preamble_len=0,
+             sync_shifts=None, hdr_nibbles=None, crc_bytes=None) -> TxFrame:
+    """A lora_hip_tx_frame_t.  hdr_nibbles / crc_bytes None: the valid header checksum / payload CRC.  The payload's bytes are
+    kept alive by the returned struct."""
+    pl = bytes(payload)
+    buf = (C.c_uint8 * max(len(pl), 1))(*pl)
+    s0, s1 = (-1, -1) if sync_shifts is None else (int(sync_shifts[0]), int(sync_shifts[1]))
+    f = TxFrame(struct_size=C.sizeof(TxFrame), bandwidth=int(bandwidth), sf=int(sf), implicit=int(bool(implicit)), cr=int(cr), crc=int(bool(crc)),
+                reduced_rate=int(bool(reduced_rate)), preamble_len=int(preamble_len), sync_shifts=(C.c_int32 * 2)(s0, s1), start=int(start),
+                freq_hz=float(freq_hz), amplitude=float(amplitude), length=len(pl), payload=C.cast(buf, C.POINTER(C.c_uint8)))
+    f._payload = buf
+    if hdr_nibbles is not None:
+        f.flags |= TX_FRAME_HDR_NIBBLES
+        f.hdr_nibbles = (C.c_uint8 * 2)(int(hdr_nibbles[0]), int(hdr_nibbles[1]))
+    if crc_bytes is not None:
+        f.flags |= TX_FRAME_CRC_BYTES
+        f.crc_bytes = (C.c_uint8 * 2)(*bytes(crc_bytes)[:2])
+    return f
+
+
+def _tx_status(L, st: int, what: str):
+    if st != 0:
+        raise LoraHipError(st, "%s: %s" % (what, L.lora_hip_strerror(st).decode()))
+
+
+def tx_encode(frame: TxFrame) -> Tuple[List[int], List[int]]:
+    """lora_hip_tx_encode (host only): (header_shifts[8], payload_shifts) as synth.encode_shifts."""
+    L = load()
+    out = (C.c_uint16 * TX_MAX_SHIFTS)()
+    nh, npay = C.c_uint32(0), C.c_uint32(0)
+    _tx_status(L, L.lora_hip_tx_encode(C.byref(frame), out, TX_MAX_SHIFTS, C.byref(nh), C.byref(npay)), "lora_hip_tx_encode")
+    return list(out[: nh.value]), list(out[nh.value: nh.value + npay.value])
+
+
+def tx_frame_items(frame: TxFrame, samp_rate: float) -> int:
+    """lora_hip_tx_frame_items (host only): items of the frame's waveform at samp_rate."""
+    L = load()
+    n = C.c_uint64(0)
+    _tx_status(L, L.lora_hip_tx_frame_items(C.byref(frame), float(samp_rate), C.byref(n)), "lora_hip_tx_frame_items")
+    return int(n.value)
+
+
+class Tx:
+    """lora_hip_tx_* (include/lora_hip_tx.h): the traffic synthesiser's stream; frames in, a wide-band capture out on the device."""
+
+    def __init__(self, samp_rate, device=0, noise_sigma=0.0, seed=0, flags=0):
+        self.L = load()
+        cfg = TxConfig(struct_size=C.sizeof(TxConfig), device=int(device), samp_rate=float(samp_rate), noise_sigma=float(noise_sigma),
+                       seed=int(seed) & 0xFFFFFFFFFFFFFFFF, flags=int(flags))
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_tx_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            self.h = None
+            raise LoraHipError(st, self.L.lora_hip_strerror(st).decode())
+        self.samp_rate, self.device = float(samp_rate), int(device)
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, "%s (%s)" % (self.L.lora_hip_strerror(st).decode(), (self.L.lora_hip_tx_last_error(self.h) or b"").decode()))
+
+    def add_frames(self, frames: Sequence[TxFrame]):
+        arr = (TxFrame * max(len(frames), 1))(*frames)
+        self._check(self.L.lora_hip_tx_add_frames(self.h, arr, len(frames)))
+
+    def generate_device(self, d_out: int, n: int, stream: int = 0):
+        self._check(self.L.lora_hip_tx_generate_device(self.h, d_out, int(n), stream))
+
+    def generate_device_raw(self, d_out: int, n: int, fmt: int, full_scale: float, stream: int = 0):
+        self._check(self.L.lora_hip_tx_generate_device_raw(self.h, d_out, int(n), int(fmt), float(full_scale), stream))
+
+    def generate(self, n: int) -> np.ndarray:
+        out = np.empty(int(n), dtype=np.complex64)
+        self._check(self.L.lora_hip_tx_generate(self.h, out.ctypes.data, int(n)))
+        return out
+
+    @property
+    def position(self) -> int:
+        return int(self.L.lora_hip_tx_position(self.h))
+
+    @property
+    def pending(self) -> int:
+        return int(self.L.lora_hip_tx_pending(self.h))
+
+    def kernel_ms(self) -> float:
+        return float(self.L.lora_hip_tx_last_kernel_ms(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.lora_hip_tx_destroy(self.h)
             self.h = None
 
     __del__ = close

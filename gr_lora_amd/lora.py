@@ -11,6 +11,9 @@ Same names, argument order and meaning as the reference module `lora`:
   lora.multi_sf_gateway_receiver(samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sfs, ...)
                                               (not upstream: every channel x every SF, one filter bank feeding one mux per SF
                                               on the device)
+  lora.modulator(samp_rate, bandwidth, sf, implicit, cr, crc, reduced_rate)
+                                              (not upstream, which only receives: the decoder's mirror, one frame per call)
+  lora.traffic_synthesizer(samp_rate, ...)    (not upstream: a wide-band capture of many concurrent emitters, made on the device)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -438,6 +441,87 @@ class multi_sf_gateway_receiver(_MsgBlock):
 
     def close(self):
         self.gateway.close()
+
+
+class traffic_synthesizer:
+    """The transmit side (include/lora_hip_tx.h, csrc/lora_tx.hip): frames placed in time and frequency, then the wide-band
+    capture they add up to, written into device memory by one kernel per generate() - the shapes multi_sf_gateway_receiver.work
+    takes.  gr_lora_amd.synth.build_wideband is the definition.  No host fall-back: without a device the constructor raises."""
+
+    def __init__(self, samp_rate, device=0, noise_sigma=0.0, seed=0):
+        self.samp_rate = float(samp_rate)
+        self.device = int(device)
+        self._h = capi.Tx(samp_rate, device=device, noise_sigma=noise_sigma, seed=seed)
+
+    def add_frame(self, payload, sf, cr, bandwidth, start, freq_hz, amplitude=1.0, crc=True, implicit=False, reduced_rate=None):
+        """One emitter: first sample at absolute index start, centre freq_hz from the capture's centre.  reduced_rate None:
+        LoRaWAN's rule (lorawan_reduced_rate).  Header checksum and payload CRC are the valid ones.
+        -> (the blob tail a decoder publishes for it, as synth.expected_frame_tail; the frame's item count)."""
+        from . import synth
+        pl = bytes(payload)
+        rr = lorawan_reduced_rate(sf, bandwidth) if reduced_rate is None else bool(reduced_rate)
+        f = capi.tx_frame(pl, sf, cr, bandwidth, start=start, freq_hz=freq_hz, amplitude=amplitude, crc=crc, implicit=implicit, reduced_rate=rr)
+        items = capi.tx_frame_items(f, self.samp_rate)
+        self._h.add_frames([f])
+        cfg = synth.TxConfig(sf=int(sf), cr=int(cr), bw=int(bandwidth), crc=bool(crc), implicit=bool(implicit), reduced_rate=rr,
+                             hdr_nibbles=synth.valid_hdr_nibbles(len(pl), int(cr), bool(crc)))
+        return synth.expected_frame_tail(pl, cfg, synth.valid_crc_bytes(pl)), items
+
+    def generate(self, n, fmt="cf32", full_scale=None, out=None):
+        """The next n items as a torch CUDA tensor, written on the current stream: complex64[n], or for fmt sc16 / sc8 / cu8 flat
+        interleaved int16 / int8 / uint8[2 n] equal to iqformat.quantize(the complex64 items, fmt, full_scale) (full_scale None:
+        the type's largest value, 32767 or 127).  out: a tensor of that dtype and size to fill instead."""
+        import torch
+        f = iqformat.format_from_name(fmt)
+        dtype = {iqformat.CF32: torch.complex64, iqformat.SC16: torch.int16, iqformat.SC8: torch.int8, iqformat.CU8: torch.uint8}[f]
+        numel = int(n) if f == iqformat.CF32 else 2 * int(n)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(numel, dtype=dtype, device=dev)
+        elif not (out.is_cuda and out.device.index == self.device and out.dtype == dtype and out.numel() == numel and out.is_contiguous()):
+            raise ValueError("traffic_synthesizer.generate: out must be a contiguous %s tensor of %d elements on cuda:%d" % (dtype, numel, self.device))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if f == iqformat.CF32:
+            self._h.generate_device(out.data_ptr(), int(n), stream)
+        else:
+            fs = float(full_scale) if full_scale is not None else (32767.0 if f == iqformat.SC16 else 127.0)
+            self._h.generate_device_raw(out.data_ptr(), int(n), f, fs, stream)
+        return out
+
+    @property
+    def position(self) -> int:
+        return self._h.position
+
+    @property
+    def pending(self) -> int:
+        return self._h.pending
+
+    def kernel_ms(self) -> float:
+        return self._h.kernel_ms()
+
+    def close(self):
+        self._h.close()
+
+
+class modulator:
+    """The mirror of `decoder`: payload bytes in, the frame's baseband samples out, made on the device by traffic_synthesizer
+    with one emitter at the capture's centre.  samp_rate / bandwidth must be an integer."""
+
+    def __init__(self, samp_rate, bandwidth, sf, implicit, cr, crc, reduced_rate=False, device=0):
+        self.samp_rate, self.bandwidth, self.sf, self.implicit, self.cr, self.crc = samp_rate, int(bandwidth), int(sf), bool(implicit), int(cr), bool(crc)
+        self.reduced_rate = bool(reduced_rate)
+        self._tx = traffic_synthesizer(samp_rate, device=device)
+
+    def modulate(self, payload, gap_items=0, amplitude=1.0, device_out=False):
+        """gap_items of silence, then the frame: complex64 numpy, or a torch CUDA tensor with device_out=True."""
+        gap = int(gap_items)
+        _tail, items = self._tx.add_frame(payload, self.sf, self.cr, self.bandwidth, self._tx.position + gap, 0.0, amplitude=amplitude, crc=self.crc,
+                                          implicit=self.implicit, reduced_rate=self.reduced_rate)
+        t = self._tx.generate(gap + items)
+        return t if device_out else t.cpu().numpy()
+
+    def close(self):
+        self._tx.close()
 
 
 class lora_receiver(_MsgBlock):

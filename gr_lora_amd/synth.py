@@ -307,3 +307,52 @@ def valid_hdr_nibbles(length: int, cr: int, crc: bool) -> Tuple[int, int]:
     c1 = bit(2) ^ bit(5) ^ bit(7) ^ bit(9) ^ bit(10) ^ bit(11)
     c0 = bit(3) ^ bit(6) ^ bit(8) ^ bit(9) ^ bit(10) ^ bit(11)
     return c4, (c3 << 3) | (c2 << 2) | (c1 << 1) | c0
+
+
+# ---- the wide-band capture: many concurrent emitters on one sample clock (the definition include/lora_hip_tx.h is held to)
+@dataclass
+class WidebandFrame:
+    """One emitter: `payload` as a frame of `cfg` (cfg.samp_rate is overridden by the capture's), its first sample at absolute
+    index `start`, centred `freq_hz` from the capture's centre."""
+    payload: bytes
+    cfg: TxConfig
+    start: int
+    freq_hz: float = 0.0
+    amplitude: float = 1.0
+    crc_bytes: bytes = b"\x70\x0d"
+
+
+def wideband_decimation(cfg: TxConfig, samp_rate: float) -> int:
+    """fs / bw, which must be an integer D with 1 <= D <= 1024 and D * 2^sf <= 2^22 (D need not be a power of two)."""
+    d = float(samp_rate) / float(cfg.bw)
+    if d != int(d) or not 1 <= int(d) <= 1024 or int(d) << cfg.sf > 1 << 22:
+        raise ValueError("samp_rate %r over bandwidth %r must be an integer in 1..1024 with at most 2^22 items per symbol" % (samp_rate, cfg.bw))
+    return int(d)
+
+
+def wideband_waveform(frame: WidebandFrame, samp_rate: float) -> np.ndarray:
+    """c_e: the frame's unit-amplitude complex64 waveform at the capture's rate."""
+    from dataclasses import replace
+    wideband_decimation(frame.cfg, samp_rate)
+    cfg = replace(frame.cfg, samp_rate=float(samp_rate))
+    return modulate_frame(*encode_shifts(frame.payload, cfg, frame.crc_bytes), cfg)
+
+
+def build_wideband(frames: Sequence[WidebandFrame], samp_rate: float, n0: int, n: int) -> np.ndarray:
+    """The float64 model of the capture on absolute sample indices n0 .. n0+n-1 (complex128[n]):
+
+        y[m] = sum over emitters e, in the order given, of
+               a_e * c_e[m - start_e] * exp(2j*pi * frac(f_e / fs * m))      for start_e <= m < start_e + len(c_e)
+
+    The oscillator runs on the absolute index m; where no emitter is active y[m] is exactly 0."""
+    n0, n = int(n0), int(n)
+    y = np.zeros(n, dtype=np.complex128)
+    for fr in frames:
+        c = wideband_waveform(fr, samp_rate).astype(np.complex128)   # (the waveform is complex64; everything after it is float64)
+        lo, hi = max(int(fr.start), n0), min(int(fr.start) + c.size, n0 + n)
+        if lo >= hi:
+            continue
+        m = np.arange(lo, hi, dtype=np.float64)
+        ph = fr.freq_hz / float(samp_rate) * m
+        y[lo - n0:hi - n0] += float(fr.amplitude) * c[lo - int(fr.start):hi - int(fr.start)] * np.exp(2j * np.pi * (ph - np.floor(ph)))
+    return y

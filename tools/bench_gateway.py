@@ -20,6 +20,14 @@ Frames: each transmitted payload counted once when found on its own (grid index,
 way the radio would deliver it (every transmitter at 2000 LSB of sc16, 12 LSB of sc8 / cu8) and fed from HOST memory in chunks
 of 2^22 items: as the integers (lora_hip_gateway_work_raw) against the same items converted to complex64 on the host beforehand
 (lora_hip_gateway_work; the conversion itself is not timed).  Wall clock, median of --runs fresh receivers after one warm-up each.
+
+    python tools/bench_gateway.py --device-synth [--seconds S] [--workload a|b] [--runs R] [--out FILE]
+
+--device-synth: the capture never exists on the host (one line per workload, "bench": "gateway_device_synth").  The same plan
+(without --seconds: frame for frame the default path's; with it: continued per channel until S seconds of air are full) goes
+through lora.traffic_synthesizer, which writes chunks of 2^22 items into one HBM buffer that multi_sf_gateway_receiver.work reads.
+Reported apart, wall clock with the device idle at each boundary: the time in generate (and its kernel time, HIP events) and
+the time in work + stop; median of --runs after one warm-up.  The default path and its cached files are untouched by it.
 """
 from __future__ import annotations
 
@@ -80,6 +88,99 @@ def synthesise(key):
         ph = (f0 + k * fs / M) / fs * np.arange(s.size, dtype=np.float64)
         wide[: s.size] += s * np.exp(2j * np.pi * (ph - np.floor(ph)))
     return wide.astype(np.complex64), expect
+
+
+def layout(key, seconds=None):
+    """The plan of synthesise(key) as frames for lora.traffic_synthesizer: ([(grid index, sf, start item, payload)], expect, items).
+    Its random draws are synthesise's in synthesise's order, so without `seconds` the frames are the default capture's; with it
+    each channel's list of SFs repeats until the next frame would not fit into `seconds` of air."""
+    from gr_lora_amd import lora, synth
+    w = WORKLOADS[key]
+    fs, ks = w["fs"], w["ks"]
+    D = int(fs / 125000)
+    tail = 3 * (1 << 12) * D
+    limit = None if seconds is None else int(seconds * fs) - tail
+    rng = np.random.default_rng(4242)
+    frames, expect, ends = [], {}, []
+
+    def place(k, sf, pos):
+        pl = bytes(rng.integers(0, 256, int(rng.integers(4, 12)), dtype=np.uint8))
+        rr = lora.lorawan_reduced_rate(sf, 125000)
+        sps = D << sf
+        gap = int(rng.integers(2 * sps, 4 * sps))
+        items = (8 + 4 + 8 + synth.payload_symbol_count(len(pl) + 2, sf, 4, rr)) * sps + sps // 4
+        end = pos + gap + items + 2 * sps
+        if limit is not None and end > limit:
+            return None
+        cfg = synth.TxConfig(sf=sf, cr=4, samp_rate=fs, reduced_rate=rr, hdr_nibbles=synth.valid_hdr_nibbles(len(pl), 4, True))
+        frames.append((k, sf, pos + gap, pl))
+        expect.setdefault((k, sf), []).append(synth.expected_frame_tail(pl, cfg, synth.valid_crc_bytes(pl)))
+        return end
+
+    plan = _plan(key, len(ks), rng)
+    for k, sfs in zip(ks, plan):
+        pos = int(rng.integers(1000, 40000))
+        for sf in sfs:
+            pos = place(k, sf, pos) or pos
+        ends.append(pos)
+    if limit is not None:
+        for i, (k, sfs) in enumerate(zip(ks, plan)):
+            j = 0
+            while True:
+                end = place(k, sfs[j % len(sfs)], ends[i])
+                if end is None:
+                    break
+                ends[i], j = end, j + 1
+    return frames, expect, (max(ends) + tail if seconds is None else int(seconds * fs))
+
+
+def run_device_synth(w, frames, n):
+    """One pass: (seconds in generate, its kernel ms, seconds in work + stop, frames, stats)."""
+    import torch
+    from gr_lora_amd import lora
+    tx = lora.traffic_synthesizer(w["fs"])
+    for k, sf, start, pl in frames:
+        tx.add_frame(pl, sf, 4, 125000, start, w["f0"] + k * w["fs"] / w["M"])
+    rx = lora.multi_sf_gateway_receiver(w["fs"], 0.0, w["f0"], w["M"], w["ks"], 125000, sfs=SFS, decimation=w["D"])
+    got = []
+    rx.subscribe("sf_frames", got.append)
+    buf = torch.empty(min(CHUNK, n), dtype=torch.complex64, device="cuda:0")
+    torch.cuda.synchronize()
+    t_syn = t_gw = ms = 0.0
+    for i in range(0, n, CHUNK):
+        m = min(CHUNK, n - i)
+        t0 = time.perf_counter()
+        tx.generate(m, out=buf[:m])                        # (returns when the items are written)
+        t1 = time.perf_counter()
+        rx.work(buf[:m])
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        t_syn, t_gw, ms = t_syn + (t1 - t0), t_gw + (t2 - t1), ms + tx.kernel_ms()
+    t0 = time.perf_counter()
+    rx.stop()
+    t_gw += time.perf_counter() - t0
+    stats = rx.stats()
+    assert tx.pending == 0, tx.pending
+    rx.close()
+    tx.close()
+    return t_syn, ms, t_gw, got, stats
+
+
+def measure_device_synth(key, runs, seconds):
+    w = WORKLOADS[key]
+    t0 = time.perf_counter()
+    frames, expect, n = layout(key, seconds)
+    t_layout = time.perf_counter() - t0
+    run_device_synth(w, frames, n)                         # warm-up
+    res = [run_device_synth(w, frames, n) for _ in range(runs)]
+    syn, ms, gw = (float(np.median([r[j] for r in res])) for j in range(3))
+    got = res[0][3]
+    return dict(bench="gateway_device_synth", workload=key, name=w["name"], samp_rate=w["fs"], channels=len(w["ks"]), items=n, air_s=round(n / w["fs"], 4),
+                chunk_items=CHUNK, transmitted=len(frames), frames_published=len(got), payloads_found=matched(got, expect),
+                layout_host_s=round(t_layout, 4), synth_s=round(syn, 4), synth_kernel_ms=round(ms, 3), gateway_s=round(gw, 4),
+                synth_runs_s=[round(r[0], 4) for r in res], gateway_runs_s=[round(r[2], 4) for r in res],
+                synth_items_per_s=round(n / syn, 1), synth_kernel_items_per_s=round(n / (ms * 1e-3), 1), gateway_items_per_s=round(n / gw, 1),
+                synth_over_gateway=round(syn / gw, 4), filterbank_calls=res[0][4]["filterbank_calls"])
 
 
 def cached(key):
@@ -232,9 +333,16 @@ def main():
     ap.add_argument("--out", help="also append the lines to this file")
     ap.add_argument("--no-baseline", action="store_true", help="the gateway only (profiler runs)")
     ap.add_argument("--format", choices=["sc16", "sc8", "cu8"], help="the host-ingest comparison: integers against complex64, both from host memory")
+    ap.add_argument("--device-synth", action="store_true", help="synthesise the capture on the device (lora.traffic_synthesizer) and feed work_device from HBM")
+    ap.add_argument("--seconds", type=float, help="with --device-synth: seconds of air (default: the default path's plan, frame for frame)")
     a = ap.parse_args()
+    if a.seconds is not None and not a.device_synth:
+        ap.error("--seconds goes with --device-synth")
     for key in a.workload or sorted(WORKLOADS):
-        line = json.dumps(measure_host_ingest(key, a.runs, a.format) if a.format else measure(key, a.runs, not a.no_baseline))
+        if a.device_synth:
+            line = json.dumps(measure_device_synth(key, a.runs, a.seconds))
+        else:
+            line = json.dumps(measure_host_ingest(key, a.runs, a.format) if a.format else measure(key, a.runs, not a.no_baseline))
         print(line, flush=True)
         if a.out:
             with open(a.out, "a") as f:
