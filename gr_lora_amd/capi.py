@@ -44,6 +44,7 @@ EXPORTS_FILTERBANK = [
     "lora_hip_filterbank_create", "lora_hip_filterbank_destroy", "lora_hip_filterbank_last_error", "lora_hip_filterbank_taps",
     "lora_hip_filterbank_output_items", "lora_hip_filterbank_run_device", "lora_hip_filterbank_run_device_rows", "lora_hip_filterbank_work",
     "lora_hip_filterbank_last_kernel_ms", "lora_hip_filterbank_run_device_raw", "lora_hip_filterbank_run_device_rows_raw", "lora_hip_filterbank_work_raw",
+    "lora_hip_filterbank_get_plan",
 ]
 
 
@@ -268,6 +269,8 @@ def load():
     L.lora_hip_filterbank_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lora_hip_filterbank_last_kernel_ms.argtypes = [vp]
     L.lora_hip_filterbank_last_kernel_ms.restype = C.c_float
+    if hasattr(L, "lora_hip_filterbank_get_plan") or not os.environ.get("LORA_HIP_LIB"):   # (as above: an older library variant does without)
+        L.lora_hip_filterbank_get_plan.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
     L.lora_hip_filterbank_run_device_rows.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp), C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.lora_hip_gateway_create.argtypes = [C.POINTER(GatewayConfig), C.POINTER(vp)]
     L.lora_hip_gateway_destroy.argtypes = [vp]
@@ -796,6 +799,12 @@ class FilterBank:
         n = C.c_size_t(0)
         self._check(self.L.lora_hip_filterbank_run_device_rows_raw(self.h, d_in, n_in, int(fmt), float(scale), ptrs, int(n_dst), int(max_out), C.byref(n), stream))
         return int(n.value)
+
+    def plan(self) -> dict:
+        """The tile shape the handle planned (lora_hip_filterbank_get_plan): cw, g, nc, q, lds_bytes."""
+        cw, g, nc, q, lds = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+        self._check(self.L.lora_hip_filterbank_get_plan(self.h, C.byref(cw), C.byref(g), C.byref(nc), C.byref(q), C.byref(lds)))
+        return dict(cw=int(cw.value), g=int(g.value), nc=int(nc.value), q=int(q.value), lds_bytes=int(lds.value))
 
     def kernel_ms(self) -> float:
         return float(self.L.lora_hip_filterbank_last_kernel_ms(self.h))

@@ -38,7 +38,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kOutD1 = 16;    // outputs per thread at decimation 1 (tile = 4096 input items); any other decimation: 1 (tile = 256 D)
-constexpr int kMaxDecim = 64;
+constexpr int kMaxDecim = (int)LORA_HIP_CHANNELIZER_MAX_DECIMATION;
+constexpr size_t kLdsMax = 160u * 1024u; // LDS per CU (gfx950)
 
 // gr::filter::firdes::low_pass(gain, fs, cutoff, transition, WIN_HAMMING) as published (GNU Radio 3.9
 // gr-filter/lib/firdes.cc): ntaps = (int)(53 * fs / (22 * transition)) made odd (the Hamming window's 53 dB),
@@ -257,24 +258,31 @@ lora_hip_status upload_channels(lora_hip_channelizer *h, bool first)
     return LORA_HIP_OK;
 }
 
+// LDS bytes of the staged tile (lora_hip_channelizer_create refuses a design above kLdsMax)
+size_t fir_lds_bytes(int tile_in, int ntaps_pad) { return (size_t)(xs_slot(tile_in + ntaps_pad - 1) + 1) * sizeof(float2); }
+
 template <int R, bool D1, int F>
-void launch_fir_as(const FirArgs &a, int n_channels, hipStream_t st)
+hipError_t launch_fir_as(const FirArgs &a, int n_channels, hipStream_t st)
 {
     const long long span_in = (a.n_out - 1) * (long long)a.decim + 1;                // input positions covered
     const unsigned tiles = (unsigned)((span_in + a.tile_in - 1) / a.tile_in);
-    const size_t lds = (size_t)(xs_slot(a.tile_in + a.ntaps - 1) + 1) * sizeof(float2);
-    if (lds > 64u * 1024u) (void)hipFuncSetAttribute((const void *)fir_mix_kernel<R, D1, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = fir_lds_bytes(a.tile_in, a.ntaps);
+    if (lds > 64u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute((const void *)fir_mix_kernel<R, D1, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL((fir_mix_kernel<R, D1, F>), dim3(tiles, (unsigned)n_channels), dim3(kThreads), lds, st, a);
+    return hipGetLastError();
 }
 
 template <int R, bool D1>
-void launch_fir(int fmt, const FirArgs &a, int n_channels, hipStream_t st)
+hipError_t launch_fir(int fmt, const FirArgs &a, int n_channels, hipStream_t st)
 {
     switch (fmt) {
-    case LORA_HIP_IQ_SC16: launch_fir_as<R, D1, LORA_HIP_IQ_SC16>(a, n_channels, st); break;
-    case LORA_HIP_IQ_SC8: launch_fir_as<R, D1, LORA_HIP_IQ_SC8>(a, n_channels, st); break;
-    case LORA_HIP_IQ_CU8: launch_fir_as<R, D1, LORA_HIP_IQ_CU8>(a, n_channels, st); break;
-    default: launch_fir_as<R, D1, LORA_HIP_IQ_CF32>(a, n_channels, st); break;
+    case LORA_HIP_IQ_SC16: return launch_fir_as<R, D1, LORA_HIP_IQ_SC16>(a, n_channels, st);
+    case LORA_HIP_IQ_SC8: return launch_fir_as<R, D1, LORA_HIP_IQ_SC8>(a, n_channels, st);
+    case LORA_HIP_IQ_CU8: return launch_fir_as<R, D1, LORA_HIP_IQ_CU8>(a, n_channels, st);
+    default: return launch_fir_as<R, D1, LORA_HIP_IQ_CF32>(a, n_channels, st);
     }
 }
 
@@ -298,21 +306,34 @@ lora_hip_status lora_hip_channelizer_create(const lora_hip_channelizer_config_t 
 {
     if (!cfg || !out || cfg->struct_size < offsetof(lora_hip_channelizer_config_t, cutoff_hz)) return LORA_HIP_ERR_ARG;
     *out = nullptr;
-    if (!cfg->channel_list || cfg->n_channels == 0 || cfg->decimation == 0 || !(cfg->samp_rate > 0.0f)) return LORA_HIP_ERR_BAD_CONFIG;
-    if (cfg->decimation > (uint32_t)kMaxDecim) return LORA_HIP_ERR_BAD_CONFIG; // the generic path stages 256 D + taps items in LDS
+    lora_hip_channelizer_config_t c{};
+    std::memcpy(&c, cfg, std::min<size_t>(cfg->struct_size, sizeof c)); // older callers: no design overrides, no flags
+    if (!c.channel_list || c.n_channels == 0 || c.decimation == 0 || !(c.samp_rate > 0.0f) || !std::isfinite(c.samp_rate)) return LORA_HIP_ERR_BAD_CONFIG;
+    if (c.decimation > (uint32_t)kMaxDecim) return LORA_HIP_ERR_BAD_CONFIG; // the generic path stages 256 D + taps items in LDS
+    if (!(c.cutoff_hz >= 0.0f) || !std::isfinite(c.cutoff_hz) || !(c.transition_hz >= 0.0f) || !std::isfinite(c.transition_hz) ||
+        (c.flags & ~LORA_HIP_CHANNELIZER_FLAG_UINT32_OFFSET) != 0)
+        return LORA_HIP_ERR_BAD_CONFIG;
+    const double cutoff = c.cutoff_hz > 0.0f ? (double)c.cutoff_hz : (double)(c.bandwidth / 2u) + 15000.0; // :46 (integer bandwidth/2)
+    const double transition = c.transition_hz > 0.0f ? (double)c.transition_hz : 10000.0;
+    // the design's size, in double before anything is converted to int: below 2 the single tap's Hamming window divides by
+    // ntaps - 1 = 0; above the limit the tap count does not fit an int, let alone the LDS
+    const double ntaps_d = 53.0 * (double)c.samp_rate / (22.0 * transition);
+    if (!(ntaps_d >= 2.0) || ntaps_d >= (double)LORA_HIP_CHANNELIZER_MAX_TAPS) return LORA_HIP_ERR_BAD_CONFIG;
+    const int ntaps = (int)ntaps_d | 1; // firdes_low_pass's count
+    const int ntaps_pad = (ntaps + 15) & ~15;
+    const int tile_in = kThreads * (c.decimation == 1 ? kOutD1 : 1) * (int)c.decimation;
+    if (fir_lds_bytes(tile_in, ntaps_pad) + sizeof(float2) > kLdsMax) return LORA_HIP_ERR_BAD_CONFIG; // the staged tile (+ the kernel's base phasor) would not launch
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) return LORA_HIP_ERR_NO_DEVICE;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || c.device < 0 || c.device >= ndev) return LORA_HIP_ERR_NO_DEVICE;
     auto *h = new lora_hip_channelizer;
-    std::memcpy(&h->cfg, cfg, std::min<size_t>(cfg->struct_size, sizeof h->cfg)); // older callers: no design overrides
-    h->device = cfg->device;
-    h->channels.assign(cfg->channel_list, cfg->channel_list + cfg->n_channels);
+    h->cfg = c;
+    h->device = c.device;
+    h->channels.assign(c.channel_list, c.channel_list + c.n_channels);
     h->cfg.channel_list = nullptr;
-    const double cutoff = h->cfg.cutoff_hz > 0.0f ? (double)h->cfg.cutoff_hz : (double)(cfg->bandwidth / 2u) + 15000.0; // :46 (integer bandwidth/2)
-    const double transition = h->cfg.transition_hz > 0.0f ? (double)h->cfg.transition_hz : 10000.0;
-    h->taps = firdes_low_pass(1.0, cfg->samp_rate, cutoff, transition);
+    h->taps = firdes_low_pass(1.0, c.samp_rate, cutoff, transition);
     h->chan.resize(h->channels.size());
     h->ntaps_pad = ((int)h->taps.size() + 15) & ~15;
-    h->tile_in = kThreads * (cfg->decimation == 1 ? kOutD1 : 1) * (int)cfg->decimation;
+    h->tile_in = tile_in;
     const int T = h->ntaps_pad;
     std::vector<float> padded(h->taps);
     padded.resize((size_t)T, 0.0f);
@@ -417,9 +438,8 @@ lora_hip_status ch_run_device(lora_hip_channelizer_t *h, const void *d_in, size_
         a.n_abs = h->n_abs; a.n_in = (long long)n_in; a.first = (D - (h->n_abs % D)) % D; a.n_out = (long long)no; a.out_stride = (long long)out_stride;
         a.ntaps = h->ntaps_pad; a.decim = (int)D; a.wtab_stride = h->wtab_stride; a.nhist = T - 1; a.tile_in = h->tile_in; a.scale = lora_iq::scale_of(fmt, scale);
         CH_TRY(h, hipEventRecord(h->ev0, st));
-        if (D == 1) launch_fir<kOutD1, true>(fmt, a, (int)h->channels.size(), st);
-        else launch_fir<1, false>(fmt, a, (int)h->channels.size(), st);
-        CH_TRY(h, hipGetLastError());
+        if (D == 1) CH_TRY(h, (launch_fir<kOutD1, true>(fmt, a, (int)h->channels.size(), st)));
+        else CH_TRY(h, (launch_fir<1, false>(fmt, a, (int)h->channels.size(), st)));
         CH_TRY(h, hipEventRecord(h->ev1, st));
     }
     // the next call's history: the last ntaps - 1 input items seen so far (integer input: converted, on the device for any n_in)

@@ -363,7 +363,7 @@ lora_hip_status lora_hip_filterbank_create(const lora_hip_filterbank_config_t *c
     const double cutoff = cfg->cutoff_hz > 0.0f ? (double)cfg->cutoff_hz : (double)(cfg->bandwidth / 2u) + 15000.0;
     const double transition = cfg->transition_hz > 0.0f ? (double)cfg->transition_hz : 10000.0;
     const double ntaps = 53.0 * cfg->samp_rate / (22.0 * transition);
-    if (!(ntaps >= 1.0) || ntaps >= (double)LORA_HIP_FILTERBANK_MAX_TAPS) return LORA_HIP_ERR_BAD_CONFIG;
+    if (!(ntaps >= 2.0) || ntaps >= (double)LORA_HIP_FILTERBANK_MAX_TAPS) return LORA_HIP_ERR_BAD_CONFIG; // (below 2: one tap, its window 0 / 0)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) return LORA_HIP_ERR_NO_DEVICE;
     auto *h = new lora_hip_filterbank;
@@ -481,6 +481,17 @@ lora_hip_status lora_hip_filterbank_work_raw(lora_hip_filterbank_t *h, const voi
 {
     const lora_hip_status s = fb_check_raw(h, in, fmt, scale);
     return s != LORA_HIP_OK ? s : fb_work(h, in, n_in, fmt, scale, out, out_stride, n_out);
+}
+
+lora_hip_status lora_hip_filterbank_get_plan(const lora_hip_filterbank_t *h, uint32_t *cw, uint32_t *g, uint32_t *nc, uint32_t *q, size_t *lds_bytes)
+{
+    if (!h) return LORA_HIP_ERR_ARG;
+    if (cw) *cw = (uint32_t)h->cw;
+    if (g) *g = (uint32_t)h->g;
+    if (nc) *nc = (uint32_t)h->nc;
+    if (q) *q = (uint32_t)h->Q;
+    if (lds_bytes) *lds_bytes = h->lds;
+    return LORA_HIP_OK;
 }
 
 float lora_hip_filterbank_last_kernel_ms(const lora_hip_filterbank_t *h) { return h ? h->last_ms : 0.0f; }

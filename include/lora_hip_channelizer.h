@@ -48,6 +48,20 @@ typedef struct lora_hip_channelizer_config {
 
 typedef struct lora_hip_channelizer lora_hip_channelizer_t;
 
+/* Limits (LORA_HIP_ERR_BAD_CONFIG outside them, before any device call). */
+#define LORA_HIP_CHANNELIZER_MAX_DECIMATION 64u /* 1 <= decimation <= 64 */
+#define LORA_HIP_CHANNELIZER_MAX_TAPS 16384u    /* 2 <= 53 samp_rate / (22 transition) < 16384 (the defaults at 1 Msps: 241 taps) */
+
+/* LORA_HIP_ERR_ARG: cfg or out NULL, struct_size below offsetof(cutoff_hz) (a caller built against the older struct passes that
+ * size: the fields from cutoff_hz on are then not read and count as 0).
+ * LORA_HIP_ERR_BAD_CONFIG, all before any device call: channel_list NULL or n_channels 0; decimation outside the limit;
+ * samp_rate not finite or <= 0; cutoff_hz or transition_hz negative or not finite; flags with a bit other than
+ * LORA_HIP_CHANNELIZER_FLAG_*; a design outside the tap limit - below 2 the design has one tap, whose Hamming window is
+ * 0 / 0, so a transition band wider than 53 samp_rate / 44 is refused, and a tiny one is refused instead of overflowing the
+ * tap count; a design whose staged tile does not fit the 160 KiB of LDS: with T the tap count rounded up to a multiple of
+ * 16 and N = 4096 at decimation 1, 256 * decimation otherwise, (N + T - 1 + (N + T - 1) / 16 + 2) * 8 bytes (64x
+ * decimation at 1 Msps: a transition band of 500 Hz, 4 819 taps, is refused; 1 kHz, 2 409 taps, fits).
+ * LORA_HIP_ERR_NO_DEVICE: no such HIP device (no CPU fallback). */
 lora_hip_status lora_hip_channelizer_create(const lora_hip_channelizer_config_t *cfg, lora_hip_channelizer_t **out);
 void            lora_hip_channelizer_destroy(lora_hip_channelizer_t *h);
 const char     *lora_hip_channelizer_last_error(const lora_hip_channelizer_t *h);

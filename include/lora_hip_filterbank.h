@@ -27,7 +27,8 @@ extern "C" {
 /* Limits (LORA_HIP_ERR_BAD_CONFIG outside them, before any device call). */
 #define LORA_HIP_FILTERBANK_MAX_GRID 256u      /* 1 <= n_grid <= 256 */
 #define LORA_HIP_FILTERBANK_MAX_DECIMATION 1024u /* 1 <= decimation <= 1024 */
-#define LORA_HIP_FILTERBANK_MAX_TAPS 16384u    /* tap count of the low-pass design (16 Msps at the defaults: 3 855) */
+#define LORA_HIP_FILTERBANK_MAX_TAPS 16384u    /* 2 <= 53 samp_rate / (22 transition) < 16384: the low-pass design's tap count (16 Msps at
+                                                * the defaults: 3 855); below 2 it has one tap, whose Hamming window is 0 / 0 */
 #define LORA_HIP_FILTERBANK_MAX_DST 8u         /* 1 <= n_dst <= 8 destinations per row (run_device_rows) */
 
 typedef struct lora_hip_filterbank_config {
@@ -94,6 +95,12 @@ lora_hip_status lora_hip_filterbank_work(lora_hip_filterbank_t *h, const float *
 /* Same with n_in host items of format fmt: the raw bytes are uploaded (2-4 times fewer than cf32) and converted by the kernel. */
 lora_hip_status lora_hip_filterbank_work_raw(lora_hip_filterbank_t *h, const void *in, size_t n_in, int fmt, float scale, float *out,
                                              size_t out_stride, size_t *n_out);
+
+/* The tile shape the handle planned from (n_grid, decimation, tap count), read-only: a workgroup takes nc chunks of cw (<= 64)
+ * output times, g chunks at a time, with q taps per polyphase branch (the tap count rounded up to q * n_grid), in lds_bytes of
+ * LDS.  Any of the output pointers may be NULL.  For tests and measurements: it says which path of the kernel a case runs. */
+lora_hip_status lora_hip_filterbank_get_plan(const lora_hip_filterbank_t *h, uint32_t *cw, uint32_t *g, uint32_t *nc, uint32_t *q,
+                                             size_t *lds_bytes);
 
 /* Kernel time of the last run (HIP events on the launch stream), for the measurements in DESIGN.md. */
 float           lora_hip_filterbank_last_kernel_ms(const lora_hip_filterbank_t *h);

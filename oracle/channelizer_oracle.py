@@ -37,10 +37,13 @@ def firdes_low_pass(gain: float, fs: float, cutoff: float, transition: float) ->
 class Channelizer:
     """Streaming restatement; one instance per channel (the reference translates channel_list[0] only)."""
 
-    def __init__(self, samp_rate, center_freq, channel_freq, bandwidth, decimation=1, uint32_offset=False):
+    def __init__(self, samp_rate, center_freq, channel_freq, bandwidth, decimation=1, uint32_offset=False, cutoff_hz=0.0, transition_hz=0.0):
         self.fs = float(samp_rate)
         self.decimation = int(decimation)
-        self.taps = firdes_low_pass(1.0, samp_rate, float(int(bandwidth) // 2) + 15000.0, 10000.0)
+        # cutoff_hz / transition_hz: the design overrides of include/lora_hip_channelizer.h (float fields), 0 = the block's own (:46)
+        cutoff = float(np.float32(cutoff_hz)) if cutoff_hz > 0 else float(int(bandwidth) // 2) + 15000.0
+        transition = float(np.float32(transition_hz)) if transition_hz > 0 else 10000.0
+        self.taps = firdes_low_pass(1.0, samp_rate, cutoff, transition)
         # d_freq_offset = channel_list[0] - center_freq with float arguments, stored in a uint32_t (channelizer_impl.cc:47,
         # channelizer_impl.h:39): float32 subtraction, truncation to whole Hz.  A negative offset wraps upstream (an
         # unsigned field; the float -> unsigned conversion of a negative value is undefined behaviour); here and in the

@@ -69,6 +69,7 @@ def test_config_struct_matches_the_header():
     (dict(f0=float("nan")), ERR_BAD_CONFIG),
     (dict(flags=1), ERR_BAD_CONFIG),
     (dict(transition_hz=10.0), ERR_BAD_CONFIG),        # 53 fs / (22 tw) taps: far above the limit
+    (dict(transition_hz=2.6e6), ERR_BAD_CONFIG),       # 53 fs / (22 tw) = 1.85: one tap, its Hamming window 0 / 0
 ])
 def test_bad_arguments_fail_before_any_device_call(lib, change, status):
     cfg, keep = _cfg(**change)
@@ -91,6 +92,7 @@ def test_null_and_short_struct(lib):
     assert lib.lora_hip_filterbank_last_error(None) == b"null handle"
     n = C.c_size_t(0)
     assert lib.lora_hip_filterbank_run_device(None, None, 0, None, 0, C.byref(n), None) == ERR_ARG
+    assert lib.lora_hip_filterbank_get_plan(None, None, None, None, None, C.byref(n)) == ERR_ARG
     assert capi.FilterBankConfig.samp_rate.size == 8 and capi.FilterBankConfig.grid_offset_hz.size == 8
 
 

@@ -1,11 +1,18 @@
 """GPU: the polyphase DFT filter bank (include/lora_hip_filterbank.h, csrc/lora_filterbank.hip) against the channeliser's float64
 oracle (oracle/channelizer_oracle.Channelizer, one instance per grid channel at center_freq 0 and f = f0 + kappa fs / M in whole
 Hz), and the gateway built on it (lora.gateway_receiver) end to end.  Tolerance: |y - y_oracle| <= 2e-5 max|y| up to 481 taps,
-1e-4 max|y| at 3 855 taps (float32 sums of that many products)."""
+1e-4 max|y| at 3 855 taps (float32 sums of that many products).  The planner's design space (PLAN_CASES: tile shapes pfb_plan chooses
+that the cases above never reach, each asserted through lora_hip_filterbank_get_plan) against tools/filterbank_model.direct, same tolerance (observed 1.6e-7 to
+1.3e-6)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from gr_lora_amd import lora, synth
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 pytestmark = pytest.mark.gpu
 
@@ -96,6 +103,150 @@ def test_streaming_chunks_vs_oracle(torch_cuda, fs, M, D, ks):
         worst = max(worst, e)
         assert e <= _tol(L), (k, e)
     print("filterbank streaming fs=%g M=%d D=%d taps=%d chunks=%d: max rel err %.2e" % (fs, M, D, L, i, worst))
+    fb.close()
+
+
+# ---- the planner's design space ------------------------------------------------------------------------------------------
+# pfb_plan picks the tile shape (g, cw, nc) from (M, D, taps); each case states the plan it was chosen for (asserted through
+# lora_hip_filterbank_get_plan: if the planner changes, these cases have to be chosen again) and what that plan reaches.
+# Reference: tools/filterbank_model.direct, the one-shot float64 definition, at f = f0 + kappa fs / M.
+#        fs    M    D    tw  taps Q  g  cw  nc  lds
+PLAN_CASES = [
+    (1e6,   1,    1, 1e5,  25, 25, 8, 64, 64, None),     # M = 1, g = 8
+    (2e6,   5,    3, 1e5,  49, 10, 7, 64, 28, None),     # even Q, g = 7
+    (2e6,  12,    7, 1e5,  49,  5, 2, 64, 10, None),     # g = 2, D coprime to M
+    (2e6,  16,    5, 1e5,  49,  4, 1, 64, 13, None),     # even Q, n_sel = 16
+    (2e6,  25,    1, 1e5,  49,  2, 2, 64, 64, None),     # Q = 2, odd M
+    (2e6,  64,    1, 4e5,  13,  1, 1, 64, 64, None),     # Q = 1 with taps < M, nc stops at 64 g
+    (2e6, 256,    1, 1e5,  49,  1, 1, 64, 56, 163696),   # M = 256, all 256 rows, 144 bytes below the LDS limit
+    (2e6, 256,  256, 1e4, 481,  2, 1, 32,  1, None),     # cw = 32, D == M
+    (2e6, 200, 1024, 1e4, 481,  3, 1, 16,  1, 161256),   # cw = 16, D > M with D mod M != 0
+    (2e6, 256, 1024, 1e4, 481,  2, 1,  8,  1, None),     # cw = 8
+]
+PLAN_F0 = 100037.0
+PLAN_IDS = ["M%d-D%d" % (c[1], c[2]) for c in PLAN_CASES]
+
+
+def _plan_rows(M, D):
+    """All rows up to M = 25 and in the M = 256, D = 1 case; otherwise both grid ends, 0 and two more."""
+    if M <= 25 or (M == 256 and D == 1):
+        return _grid(M)
+    lo, hi = -(M // 2), (M + 1) // 2 - 1
+    return [lo, -(M * 3 // 10), 0, M // 6 - 1, hi]
+
+
+def _plan_fb(case):
+    from gr_lora_amd import capi
+    fs, M, D, tw, ntaps, Q, g, cw, nc, lds = case
+    ks = _plan_rows(M, D)
+    fb = capi.FilterBank(fs, PLAN_F0, M, ks, 125000, D, cutoff_hz=200e3, transition_hz=tw)
+    p = fb.plan()
+    assert fb.taps().size == ntaps
+    assert (p["q"], p["g"], p["cw"], p["nc"]) == (Q, g, cw, nc), p
+    assert p["lds_bytes"] <= 160 * 1024 and (lds is None or p["lds_bytes"] == lds), p
+    return fb, ks, p
+
+
+def _direct_rows(fs, M, D, ks, taps, x):
+    from filterbank_model import direct
+    return np.stack([direct(fs, PLAN_F0 + k * fs / M, taps, D, x) for k in ks])
+
+
+def _stream_chunks(rng, n, D, L):
+    """The chunk recipe of test_streaming_chunks_vs_oracle: [(pos, size)]."""
+    fixed = [1, max(D - 1, 1), L - 1, L // 3, 2 * D + 1]
+    out, pos, i = [], 0, 0
+    while pos < n:
+        c = fixed[i] if i < len(fixed) else int(rng.integers(1, 3 * L))
+        c = min(c, n - pos)
+        out.append((pos, c))
+        pos += c
+        i += 1
+    return out
+
+
+@pytest.mark.parametrize("case", PLAN_CASES, ids=PLAN_IDS)
+def test_plan_space_one_shot_vs_model(torch_cuda, case):
+    """Two full tiles, half a tile and one more output, in one call."""
+    fs, M, D, tw, ntaps = case[:5]
+    fb, ks, p = _plan_fb(case)
+    T = p["cw"] * p["nc"]
+    n_in = (2 * T + T // 2 + 1) * D + 1
+    assert n_in <= 45_000
+    x = _noise(np.random.default_rng(M * 1000 + D), n_in)
+    y = fb.work(x)
+    assert y.shape == (len(ks), (n_in + D - 1) // D) and np.isfinite(y.view(np.float32)).all()
+    want = _direct_rows(fs, M, D, ks, fb.taps(), x)
+    errs = [_err(y[i], want[i]) for i in range(len(ks))]
+    print("filterbank plan one-shot fs=%g M=%d D=%d taps=%d plan=%s rows=%d n_in=%d: max rel err %.2e" % (fs, M, D, ntaps, p, len(ks), n_in, max(errs)))
+    assert max(errs) <= _tol(ntaps), (ks[int(np.argmax(errs))], max(errs))
+    fb.close()
+
+
+STREAM_PLAN_CASES = [c for c in PLAN_CASES if (c[1], c[2]) in ((5, 3), (256, 256), (200, 1024))]
+ROWS_PLAN_CASES = [c for c in PLAN_CASES if (c[1], c[2]) in ((256, 256), (200, 1024), (256, 1024))]
+
+
+def _stream_len(p, D):
+    """Two tiles and a half of input, 12 000 items at least, so that the random chunks follow the fixed ones for a while."""
+    return max(5 * p["cw"] * p["nc"] * D // 2 + 1, 12_000)
+
+
+@pytest.mark.parametrize("case", STREAM_PLAN_CASES, ids=["M%d-D%d" % (c[1], c[2]) for c in STREAM_PLAN_CASES])
+def test_plan_space_streaming_vs_model(torch_cuda, case):
+    """The same plans fed in chunks (shorter than D, shorter than the filter, random): the concatenated stream is the one-shot
+    definition's."""
+    fs, M, D, tw, ntaps = case[:5]
+    fb, ks, p = _plan_fb(case)
+    rng = np.random.default_rng(7 * M + D)
+    n = _stream_len(p, D)
+    assert n <= 45_000
+    x = _noise(rng, n)
+    chunks = _stream_chunks(rng, n, D, ntaps)
+    y = np.concatenate([fb.work(x[pos:pos + c]) for pos, c in chunks], axis=1)
+    want = _direct_rows(fs, M, D, ks, fb.taps(), x)
+    errs = [_err(y[i], want[i]) for i in range(len(ks))]
+    print("filterbank plan streaming fs=%g M=%d D=%d taps=%d chunks=%d n_in=%d: max rel err %.2e" % (fs, M, D, ntaps, len(chunks), n, max(errs)))
+    assert max(errs) <= _tol(ntaps), (ks[int(np.argmax(errs))], max(errs))
+    fb.close()
+
+
+@pytest.mark.parametrize("case", ROWS_PLAN_CASES, ids=["M%d-D%d" % (c[1], c[2]) for c in ROWS_PLAN_CASES])
+def test_plan_space_rows_mode_equals_run_device(torch_cuda, case):
+    """run_device_rows at cw < 64 (the kernel reads the row pointers from lanes that hold no output; at cw = 8 the second
+    destination's lie outside the active lanes), 2 destinations, fed the same chunks as run_device: the same bits in both, and
+    nothing written around them."""
+    torch = torch_cuda
+    fs, M, D, tw, ntaps = case[:5]
+    fb, ks, p = _plan_fb(case)
+    ref, _, _ = _plan_fb(case)
+    rng = np.random.default_rng(11 * M + D)
+    n = _stream_len(p, D)
+    x = _noise(rng, n)
+    chunks = _stream_chunks(rng, n, D, ntaps)
+    nch, total, pad = len(ks), (n + D - 1) // D, 5
+    d_x = torch.from_numpy(x.view(np.float32)).to("cuda")
+    out_ref = torch.full((nch, 2 * total), float("nan"), dtype=torch.float32, device="cuda")
+    stride = total + 2 * pad
+    bufs = [torch.full((nch * 2 * stride,), float("nan"), dtype=torch.float32, device="cuda") for _ in range(2)]
+    stream = torch.cuda.current_stream().cuda_stream
+    got = 0
+    for pos, c in chunks:
+        no = fb.output_items(c)
+        ptrs = [bufs[d].data_ptr() + 8 * (r * stride + pad + got) for d in range(2) for r in range(nch)]
+        assert fb.run_device_rows(d_x.data_ptr() + 8 * pos, c, ptrs, 2, no, stream) == no
+        assert ref.run_device(d_x.data_ptr() + 8 * pos, c, out_ref.data_ptr() + 8 * got, total, stream) == no
+        got += no
+    assert got == total and not torch.isnan(out_ref).any()
+    want = out_ref.view(torch.int32).cpu()
+    for d in range(2):
+        b = bufs[d].view(nch, 2 * stride).cpu()
+        assert torch.equal(b[:, 2 * pad:2 * (pad + total)].contiguous().view(torch.int32), want), d
+        assert torch.isnan(b[:, :2 * pad]).all() and torch.isnan(b[:, 2 * (pad + total):]).all(), d
+    e = _err(out_ref.cpu().numpy().view(np.complex64), _direct_rows(fs, M, D, ks, fb.taps(), x))
+    print("filterbank plan rows fs=%g M=%d D=%d taps=%d chunks=%d: max rel err %.2e" % (fs, M, D, ntaps, len(chunks), e))
+    assert e <= _tol(ntaps)
+    ref.close()
     fb.close()
 
 
