@@ -60,6 +60,12 @@ EXPORTS_TX = [
     "lora_hip_tx_last_kernel_ms",
 ]
 
+EXPORTS_LINK = [
+    "lora_hip_link_measure_device", "lora_hip_link_combine", "lora_hip_link_enable", "lora_hip_link_poll_frame", "lora_hip_link_drain_frames",
+    "lora_hip_link_mux_enable", "lora_hip_link_mux_poll_frame", "lora_hip_link_gateway_enable", "lora_hip_link_gateway_poll_frame",
+    "lora_hip_link_stats",
+]
+
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
 GATEWAY_MAX_DECODERS = 7      # include/lora_hip_gateway.h
 GATEWAY_STEP_OUTPUTS = 65536  # include/lora_hip_gateway.h
@@ -154,6 +160,29 @@ class TxFrame(C.Structure):
 class TxConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("samp_rate", C.c_double), ("noise_sigma", C.c_double),
                 ("seed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+LINK_FLAG_PREAMBLE, LINK_FLAG_SYNC, LINK_FLAG_SFD = 1, 2, 4  # lora_hip_link_metrics_t.flags (include/lora_hip_link.h)
+
+
+class LinkWindow(C.Structure):
+    _fields_ = [("peak_bin", C.c_int32), ("frac", C.c_float), ("lobe_power", C.c_float), ("total_power", C.c_float), ("peak_power", C.c_float),
+                ("valid", C.c_uint32)]
+
+
+class LinkMetrics(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved0", C.c_uint32), ("signal_power", C.c_double), ("noise_power", C.c_double),
+                ("rssi_dbfs", C.c_double), ("snr_db", C.c_double), ("cfo_bins", C.c_double), ("cfo_hz", C.c_double),
+                ("timing_samples", C.c_double), ("sync_shift", C.c_int32 * 2), ("reserved", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k in ("flags", "signal_power", "noise_power", "rssi_dbfs", "snr_db", "cfo_bins", "cfo_hz", "timing_samples")}
+        d["sync_shift"] = [int(self.sync_shift[0]), int(self.sync_shift[1])]
+        return d
+
+
+class LinkRequest(C.Structure):
+    _fields_ = [("stream", C.c_uint32), ("reserved", C.c_uint32), ("header_pos", C.c_int64)]
 
 
 class LoraHipError(RuntimeError):
@@ -315,6 +344,18 @@ def load():
         L.lora_hip_tx_pending.restype = C.c_size_t
         L.lora_hip_tx_last_kernel_ms.argtypes = [vp]
         L.lora_hip_tx_last_kernel_ms.restype = C.c_float
+    if hasattr(L, "lora_hip_link_enable") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        L.lora_hip_link_measure_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.POINTER(LinkRequest), C.c_size_t, C.POINTER(LinkMetrics),
+                                                   C.POINTER(LinkWindow), vp]
+        L.lora_hip_link_combine.argtypes = [C.POINTER(LinkWindow), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(LinkMetrics)]
+        L.lora_hip_link_enable.argtypes = [vp, C.c_int]
+        L.lora_hip_link_poll_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(FrameInfo), C.POINTER(LinkMetrics)]
+        L.lora_hip_link_drain_frames.argtypes = [vp, vp, C.c_size_t, C.POINTER(FrameInfo), C.POINTER(LinkMetrics), C.c_size_t, C.POINTER(C.c_size_t)]
+        L.lora_hip_link_mux_enable.argtypes = [vp, C.c_int]
+        L.lora_hip_link_mux_poll_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(FrameInfo), C.POINTER(LinkMetrics)]
+        L.lora_hip_link_gateway_enable.argtypes = [vp, C.c_int]
+        L.lora_hip_link_gateway_poll_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(GatewayFrameInfo), C.POINTER(LinkMetrics)]
+        L.lora_hip_link_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -532,6 +573,55 @@ class Handle:
             if n.value == 0:
                 return out
 
+    def enable_link(self, on: bool = True):
+        """lora_hip_link_enable: every frame published from now on carries link metrics (drain_link)."""
+        self._check(self.L.lora_hip_link_enable(self.h, int(bool(on))))
+
+    def drain_link(self) -> List[Tuple[bytes, FrameInfo, "LinkMetrics"]]:
+        """All queued frames with their link metrics (flags == 0: published while link metrics were off)."""
+        out = []
+        while True:
+            k = min(self.frames_available(), 4096)
+            if k == 0:
+                return out
+            buf = (C.c_uint8 * (k * 280))()
+            infos, mets = (FrameInfo * k)(), (LinkMetrics * k)()
+            n = C.c_size_t(0)
+            self._check(self.L.lora_hip_link_drain_frames(self.h, buf, k * 280, infos, mets, k, C.byref(n)))
+            raw, off = bytes(buf), 0
+            for i in range(n.value):
+                ln = infos[i].length
+                out.append((raw[off:off + ln], FrameInfo(infos[i].stream, ln, infos[i].header_pos, infos[i].end_pos), LinkMetrics.from_buffer_copy(mets[i])))
+                off += ln
+            if n.value == 0:
+                return out
+
+    def poll_frame_link(self):
+        buf = (C.c_uint8 * 320)()
+        n, info, met = C.c_size_t(0), FrameInfo(), LinkMetrics()
+        self._check(self.L.lora_hip_link_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info), C.byref(met)))
+        return None if n.value == 0 else (bytes(buf[: n.value]), info, met)
+
+    def measure_link_device(self, dev_ptr: int, total_items: int, offs: Sequence[int], lens: Sequence[int], requests, stream: int = 0, windows: bool = False):
+        """lora_hip_link_measure_device: requests = (stream, header_pos) pairs -> list of LinkMetrics (and, with windows, the
+        6 * n LinkWindow records)."""
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        l = np.ascontiguousarray(lens, dtype=np.uint64)
+        n = len(requests)
+        arr = (LinkRequest * max(n, 1))()
+        for i, (st, hp) in enumerate(requests):
+            arr[i].stream, arr[i].header_pos = int(st), int(hp)
+        mets = (LinkMetrics * max(n, 1))()
+        wins = (LinkWindow * max(6 * n, 1))() if windows else None
+        self._check(self.L.lora_hip_link_measure_device(self.h, dev_ptr, total_items, o.ctypes.data, l.ctypes.data, o.size, arr, n, mets, wins, stream))
+        m = [LinkMetrics.from_buffer_copy(mets[i]) for i in range(n)]
+        return (m, [LinkWindow.from_buffer_copy(wins[i]) for i in range(6 * n)]) if windows else m
+
+    def link_stats(self) -> dict:
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
+        self._check(self.L.lora_hip_link_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"launches": int(a.value), "frames": int(b.value), "kernel_ms": float(c.value)}
+
     INFO_DTYPE = np.dtype([("stream", "<u4"), ("length", "<u4"), ("header_pos", "<i8"), ("end_pos", "<i8")])
 
     def drain_raw(self):
@@ -643,6 +733,18 @@ class Mux:
             info = FrameInfo()
             self._check(self.L.lora_hip_mux_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info)))
             out.append((bytes(buf[: n.value]), info))
+        return out
+
+    def enable_link(self, on: bool = True):
+        self._check(self.L.lora_hip_link_mux_enable(self.h, int(bool(on))))
+
+    def drain_link(self) -> List[Tuple[bytes, FrameInfo, "LinkMetrics"]]:
+        out = []
+        buf = (C.c_uint8 * 320)()
+        while self.L.lora_hip_mux_frames_available(self.h):
+            n, info, met = C.c_size_t(0), FrameInfo(), LinkMetrics()
+            self._check(self.L.lora_hip_link_mux_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info), C.byref(met)))
+            out.append((bytes(buf[: n.value]), info, met))
         return out
 
     def close(self):
@@ -885,6 +987,18 @@ class Gateway:
             info = GatewayFrameInfo()
             self._check(self.L.lora_hip_gateway_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info)))
             out.append((bytes(buf[: n.value]), info))
+        return out
+
+    def enable_link(self, on: bool = True):
+        self._check(self.L.lora_hip_link_gateway_enable(self.h, int(bool(on))))
+
+    def drain_link(self) -> List[Tuple[bytes, GatewayFrameInfo, "LinkMetrics"]]:
+        out = []
+        buf = (C.c_uint8 * 320)()
+        while self.L.lora_hip_gateway_frames_available(self.h):
+            n, info, met = C.c_size_t(0), GatewayFrameInfo(), LinkMetrics()
+            self._check(self.L.lora_hip_link_gateway_poll_frame(self.h, buf, 320, C.byref(n), C.byref(info), C.byref(met)))
+            out.append((bytes(buf[: n.value]), info, met))
         return out
 
     def stats(self) -> dict:

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/lora_hip_gateway.h"
+#include "../../include/lora_hip_link.h"
 #include "lora_mux_dev.h"
 #include "lora_iq.h"
 
@@ -318,6 +319,38 @@ lora_hip_status lora_hip_gateway_poll_frame(lora_hip_gateway_t *g, uint8_t *buf,
         if (!lora_hip_mux_frames_available(g->mux[i])) continue;
         lora_hip_frame_info_t fi{};
         GW_MUX(g, i, lora_hip_mux_poll_frame(g->mux[i], buf, cap, len, &fi));
+        if (info) {
+            *info = lora_hip_gateway_frame_info_t{};
+            info->row = fi.stream;
+            info->grid_index = fi.stream < g->channels.size() ? g->channels[fi.stream] : 0;
+            info->sf = g->dec[i].sf;
+            info->decoder = (uint32_t)i;
+            info->length = fi.length;
+            info->header_pos = fi.header_pos;
+            info->end_pos = fi.end_pos;
+        }
+        return LORA_HIP_OK;
+    }
+    return LORA_HIP_OK;
+}
+
+// link metrics (include/lora_hip_link.h): both only forward to every decoder's mux
+lora_hip_status lora_hip_link_gateway_enable(lora_hip_gateway_t *g, int on)
+{
+    if (!g) return LORA_HIP_ERR_ARG;
+    for (size_t i = 0; i < g->mux.size(); i++) GW_MUX(g, i, lora_hip_link_mux_enable(g->mux[i], on));
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_link_gateway_poll_frame(lora_hip_gateway_t *g, uint8_t *buf, size_t cap, size_t *len, lora_hip_gateway_frame_info_t *info,
+                                                 lora_hip_link_metrics_t *metrics)
+{
+    if (!g || !len || !metrics) return LORA_HIP_ERR_ARG;
+    *len = 0;
+    for (size_t i = 0; i < g->mux.size(); i++) {
+        if (!lora_hip_mux_frames_available(g->mux[i])) continue;
+        lora_hip_frame_info_t fi{};
+        GW_MUX(g, i, lora_hip_link_mux_poll_frame(g->mux[i], buf, cap, len, &fi, metrics));
         if (info) {
             *info = lora_hip_gateway_frame_info_t{};
             info->row = fi.stream;

@@ -20,7 +20,9 @@
 #include <vector>
 
 #include "../../include/lora_hip.h"
+#include "../../include/lora_hip_link.h"
 #include "lora_device.h"
+#include "lora_link.h"
 #include "lora_stitch.hpp"
 #include "lora_mux_dev.h"
 #include "lora_iq.h"
@@ -34,7 +36,7 @@ constexpr uint32_t kWorkBudget = 64u * 1024u + 64u; // LDS work area cap (bytes)
 
 // Published frames wait here for poll/drain: blobs back to back in one byte arena (no allocation per frame).
 struct FrameQueue {
-    struct Ref { size_t off; lora_hip_frame_info_t info; };
+    struct Ref { size_t off; lora_hip_frame_info_t info; lora_hip_link_metrics_t link; }; // link.flags == 0: not measured
     std::vector<uint8_t> bytes;
     std::vector<Ref> refs;
     size_t head = 0; // first frame not yet handed out
@@ -44,7 +46,7 @@ struct FrameQueue {
     {
         const size_t off = bytes.size();
         bytes.resize(off + len, 0);
-        refs.push_back(Ref{off, info});
+        refs.push_back(Ref{off, info, lora_hip_link_metrics_t{}});
         return bytes.data() + off;
     }
     const Ref &front() const { return refs[head]; }
@@ -212,6 +214,20 @@ struct lora_hip_decoder {
     DevBuf<uint32_t> d_alt_bins;
     hipStream_t pay_stream = nullptr;  // the payload pass runs here, beside the explicit probes of the same pass on the caller's stream
     hipEvent_t ev_pay0 = nullptr, ev_pay1 = nullptr, ev_pay_done = nullptr;
+    // link metrics (include/lora_hip_link.h): off unless lora_hip_link_enable turned them on; the table and the events are made on first use
+    struct Link {
+        struct Pending { size_t ref; uint64_t off, len; int64_t hdr_pos; }; // a frame pushed by the pass being collected: its stream inside the pass's IQ
+        bool on = false;
+        float *d_hann = nullptr;
+        DevBuf<LinkWindowDesc> d_wins;
+        DevBuf<LinkWindowRec> d_recs;
+        std::vector<LinkWindowDesc> h_wins;
+        std::vector<lora_hip_link_window_t> h_recs;
+        std::vector<Pending> pending;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        uint64_t launches = 0, frames = 0;
+        double kernel_ms = 0.0;
+    } link;
     struct PayState { std::vector<uint32_t> active; size_t used = 0, cap_sym = 0, n_sym = 0; int round = 0; float ms = 0.0f; bool open = false; } pay;
 };
 
@@ -424,6 +440,7 @@ void publish(lora_hip_decoder *h, const AttemptRec &r, StreamDesc &sd)
     uint8_t *blob = h->frames.push(info.length, info); // zero-filled loratap header
     blob[13] = snr_byte(sd.pwr.snr);                   // loratap_header.rssi.snr, byte offset 13
     std::memcpy(blob + kLoratapLen, r.frame, r.frame_len);
+    if (h->link.on) h->link.pending.push_back({h->frames.refs.size() - 1u, sd.off, sd.len, r.hdr_pos}); // measured when the pass has been collected (link_measure_pending)
 }
 
 // Launches the walker over a set of jobs (run_jobs_begin) and brings the results back to the host (run_jobs_end).
@@ -945,6 +962,119 @@ struct DeviceEnv {
     double walker_ms() const { return h->timing.walker_ms; }
 };
 
+// ---- link metrics (include/lora_hip_link.h; kernel: lora_link.hip; definition: gr_lora_amd/linkmetrics.py) ---------------------
+constexpr double kLinkNorm = 0.375 * 2.0; // power gain of the Hann window (mean of w^2) times |d_downchirp|^2 (the reference's 1 + 1j)
+
+void link_combine(const lora_hip_link_window_t *w, uint32_t sps, uint32_t nbins, double bandwidth, lora_hip_link_metrics_t *out)
+{
+    *out = lora_hip_link_metrics_t{};
+    const double N = (double)nbins, D = (double)sps / N, norm = kLinkNorm * (double)sps * (double)sps;
+    auto wrap = [N](double v) { v = std::fmod(v + 0.5 * N, N); if (v < 0.0) v += N; return v - 0.5 * N; };
+    bool pair[3];
+    double pos[6] = {0, 0, 0, 0, 0, 0}, mid[3] = {0, 0, 0};
+    for (int p = 0; p < 3; p++) {
+        pair[p] = w[2 * p].valid != 0u && w[2 * p + 1].valid != 0u;
+        if (!pair[p]) continue;
+        out->flags |= 1u << p;
+        for (int k = 0; k < 2; k++) pos[2 * p + k] = wrap((double)w[2 * p + k].peak_bin + (double)w[2 * p + k].frac);
+        mid[p] = wrap(pos[2 * p] + 0.5 * wrap(pos[2 * p + 1] - pos[2 * p])); // (the mean of two positions either side of the wrap is not 0)
+    }
+    double s_sum = 0.0, nb_sum = 0.0;
+    int cnt = 0;
+    for (int p = 0; p < 3; p += 2) {
+        if (!pair[p]) continue;
+        for (int k = 0; k < 2; k++) {
+            const lora_hip_link_window_t &x = w[2 * p + k];
+            const double nb = std::max(((double)x.total_power - (double)x.lobe_power) / (N - 7.0), 0.0);
+            s_sum += std::max((double)x.lobe_power - 7.0 * nb, 0.0);
+            nb_sum += nb;
+            cnt++;
+        }
+    }
+    out->rssi_dbfs = out->snr_db = LORA_HIP_LINK_FLOOR_DB;
+    if (cnt) {
+        out->signal_power = s_sum / cnt / norm;
+        out->noise_power = nb_sum * N / cnt / norm;
+        if (out->signal_power > 0.0) {
+            out->rssi_dbfs = std::max(10.0 * std::log10(out->signal_power), LORA_HIP_LINK_FLOOR_DB);
+            out->snr_db = out->noise_power > 0.0 ? std::min(std::max(10.0 * std::log10(out->signal_power / out->noise_power), LORA_HIP_LINK_FLOOR_DB), -LORA_HIP_LINK_FLOOR_DB)
+                                                 : -LORA_HIP_LINK_FLOOR_DB;
+        }
+    }
+    if (pair[0] && pair[2]) {
+        out->cfo_bins = wrap(0.5 * wrap(mid[0] - mid[2]));
+        out->cfo_hz = out->cfo_bins * bandwidth / N;
+        out->timing_samples = wrap(mid[2] + 0.5 * wrap(mid[0] - mid[2])) * D;
+    }
+    if (pair[0] && pair[1])
+        for (int k = 0; k < 2; k++) {
+            const long long r = (long long)std::floor(wrap(pos[2 + k] - mid[0]) + 0.5);
+            out->sync_shift[k] = (int32_t)(((r % (long long)nbins) + (long long)nbins) % (long long)nbins);
+        }
+}
+
+struct LinkReq { uint64_t off, len; int64_t hdr_pos; }; // a frame: its stream inside the IQ buffer (checked by the caller), its first header symbol inside the stream
+
+// Measures n frames of d_iq on st and waits: metrics[n], and the 6 n window records if windows is not null.
+lora_hip_status link_run(lora_hip_decoder *h, const float2 *d_iq, const LinkReq *req, size_t n, lora_hip_link_metrics_t *metrics, lora_hip_link_window_t *windows, hipStream_t st)
+{
+    static_assert(sizeof(lora_hip_link_window_t) == 24 && sizeof(LinkWindowRec) == 24, "kernel record layout");
+    if (n == 0) return LORA_HIP_OK;
+    lora_hip_decoder::Link &L = h->link;
+    const int64_t sps = h->P.sps;
+    if (!L.d_hann) { // w[n] = 0.5 - 0.5 cos(2 pi (n + 0.5) / sps), evaluated in double
+        std::vector<float> w((size_t)sps);
+        for (int64_t i = 0; i < sps; i++) w[(size_t)i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * ((double)i + 0.5) / (double)sps));
+        const lora_hip_status s = upload(h, &L.d_hann, w);
+        if (s != LORA_HIP_OK) return s;
+    }
+    if (!L.ev0) { HIP_TRY(h, hipEventCreate(&L.ev0)); HIP_TRY(h, hipEventCreate(&L.ev1)); }
+    const size_t nw = n * LORA_HIP_LINK_WINDOWS;
+    if (nw > 0x7fffffffu) return fail(h, LORA_HIP_ERR_ARG, "too many frames for one link measurement");
+    L.h_wins.assign(nw, LinkWindowDesc{});
+    L.h_recs.resize(nw);
+    static const int64_t quarter[3] = {25, 17, 9}; // the pairs start 25/4, 17/4 and 9/4 symbols before the header
+    for (size_t i = 0; i < n; i++)
+        for (int p = 0; p < 3; p++)
+            for (int k = 0; k < 2; k++) {
+                LinkWindowDesc &d = L.h_wins[i * LORA_HIP_LINK_WINDOWS + 2 * p + k];
+                if (req[i].hdr_pos < -((int64_t)1 << 60) || req[i].hdr_pos > ((int64_t)1 << 60)) continue; // (no overflow below)
+                const int64_t start = req[i].hdr_pos - (quarter[p] * sps) / 4 + k * sps;
+                if (start < 0 || (uint64_t)start + (uint64_t)sps > req[i].len) continue; // invalid: never read
+                d.offset = (int64_t)req[i].off + start; d.valid = 1u; d.conj = p == 2 ? 1u : 0u;
+            }
+    HIP_TRY(h, L.d_wins.reserve(nw));
+    HIP_TRY(h, L.d_recs.reserve(nw));
+    HIP_TRY(h, hipMemcpyAsync(L.d_wins.p, L.h_wins.data(), nw * sizeof(LinkWindowDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemsetAsync(L.d_recs.p, 0, nw * sizeof(LinkWindowRec), st));
+    HIP_TRY(h, hipEventRecord(L.ev0, st));
+    if (launch_link_windows(h->P, L.d_hann, d_iq, L.d_wins.p, (uint32_t)nw, L.d_recs.p, st) != 0)
+        return fail(h, LORA_HIP_ERR_HIP, "link launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(h, hipEventRecord(L.ev1, st));
+    HIP_TRY(h, hipMemcpyAsync(L.h_recs.data(), L.d_recs.p, nw * sizeof(LinkWindowRec), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIP_TRY(h, hipEventElapsedTime(&ms, L.ev0, L.ev1));
+    L.launches++; L.frames += n; L.kernel_ms += (double)ms;
+    for (size_t i = 0; i < n; i++) link_combine(&L.h_recs[i * LORA_HIP_LINK_WINDOWS], h->P.sps, h->P.nbins, (double)h->cfg.bandwidth, &metrics[i]);
+    if (windows) std::copy(L.h_recs.begin(), L.h_recs.end(), windows);
+    return LORA_HIP_OK;
+}
+
+// the frames published since the last call (publish): one launch for all of them, their queue entries filled before this returns
+lora_hip_status link_measure_pending(lora_hip_decoder *h, const float2 *d_iq, hipStream_t st)
+{
+    std::vector<lora_hip_decoder::Link::Pending> pend;
+    pend.swap(h->link.pending);
+    std::vector<LinkReq> req(pend.size());
+    std::vector<lora_hip_link_metrics_t> met(pend.size());
+    for (size_t i = 0; i < pend.size(); i++) req[i] = LinkReq{pend[i].off, pend[i].len, pend[i].hdr_pos};
+    const lora_hip_status s = link_run(h, d_iq, req.data(), req.size(), met.data(), nullptr, st);
+    if (s != LORA_HIP_OK) return s;
+    for (size_t i = 0; i < pend.size(); i++) h->frames.refs[pend[i].ref].link = met[i];
+    return LORA_HIP_OK;
+}
+
 // the status of a failed scheduler call: that of the HIP call that left a message, else an internal error
 lora_hip_status scheduler_failed(lora_hip_decoder *h)
 {
@@ -959,6 +1089,7 @@ lora_hip_status pass_begin(lora_hip_decoder *h, const float2 *d_iq, hipStream_t 
     h->pass_iq = d_iq; h->pass_st = st;
     h->iq_ready = iq_ready;
     h->err.clear();
+    h->link.pending.clear(); // (what a failed pass left behind)
     DeviceEnv env{h, d_iq, st};
     const int rc = lora_hip::decode_begin(env, h->pass_streams, h->pass);
     h->iq_ready = false;
@@ -972,7 +1103,9 @@ lora_hip_status pass_end(lora_hip_decoder *h)
     h->pass_open = false;
     h->err.clear();
     DeviceEnv env{h, h->pass_iq, h->pass_st};
-    return lora_hip::decode_end(env, h->pass_streams, h->pass) == 0 ? LORA_HIP_OK : scheduler_failed(h);
+    if (lora_hip::decode_end(env, h->pass_streams, h->pass) != 0) { h->link.pending.clear(); return scheduler_failed(h); }
+    // link metrics of the frames this pass published: here, while the pass's buffer is what the pass read (the pipeline may move it afterwards)
+    return h->link.pending.empty() ? LORA_HIP_OK : link_measure_pending(h, h->pass_iq, h->pass_st);
 }
 
 // ---- the streaming pipeline: lora_hip_work's stream, or a mux's channels, in chunks decoded while the next ones arrive ------------
@@ -1193,6 +1326,10 @@ void lora_hip_destroy(lora_hip_decoder_t *h)
     if (h->d_up_ifreq) (void)hipFree(h->d_up_ifreq);
     if (h->d_down_ifreq) (void)hipFree(h->d_down_ifreq);
     if (h->d_up_ifreq_v) (void)hipFree(h->d_up_ifreq_v);
+    if (h->link.d_hann) (void)hipFree(h->link.d_hann);
+    h->link.d_wins.release(); h->link.d_recs.release();
+    for (hipEvent_t e : {h->link.ev0, h->link.ev1})
+        if (e) (void)hipEventDestroy(e);
     h->p_pay_off.release(); h->p_pay_desc.release(); h->p_pay_out.release(); h->d_fine.release(); h->d_alt_shift.release(); h->d_alt_bins.release(); h->d_alt_fine.release();
     h->d_jobs.release(); h->d_results.release(); h->d_recs.release(); h->d_scratch.release();
     h->d_trace.release(); h->d_staging.release(); h->d_offsets.release(); h->d_bins.release();
@@ -2035,9 +2172,10 @@ lora_hip_status lora_hip_decode_at_headers_device(lora_hip_decoder_t *h, const v
         if (r.status != kAttemptFrame) continue; // (ran out of data mid-packet)
         StreamDesc sd{};
         sd.id = jobs[i].stream_id; sd.abs_base = 0;
+        sd.off = jobs[i].stream_off; sd.len = jobs[i].stream_len;
         publish(h, r, sd);
     }
-    return LORA_HIP_OK;
+    return h->link.pending.empty() ? LORA_HIP_OK : link_measure_pending(h, (const float2 *)d_iq, (hipStream_t)hip_stream);
 }
 
 lora_hip_status lora_hip_last_plan(const lora_hip_decoder_t *h, uint32_t *burst_aware, uint32_t *segments)
@@ -2080,6 +2218,85 @@ size_t lora_hip_trace(const lora_hip_decoder_t *h, const lora_hip_step_t **steps
 void lora_hip_trace_clear(lora_hip_decoder_t *h)
 {
     if (h) h->trace.clear();
+}
+
+// ---- link metrics (include/lora_hip_link.h) ----------------------------------------------------------------------------------
+lora_hip_status lora_hip_link_combine(const lora_hip_link_window_t *windows, uint32_t sps, uint32_t nbins, double bandwidth, lora_hip_link_metrics_t *out)
+{
+    if (!windows || !out || nbins < 16u || sps < nbins || (sps & (sps - 1u)) != 0u || (nbins & (nbins - 1u)) != 0u) return LORA_HIP_ERR_ARG;
+    link_combine(windows, sps, nbins, bandwidth, out);
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_link_measure_device(lora_hip_decoder_t *h, const void *d_iq, size_t total_items, const uint64_t *stream_off,
+                                             const uint64_t *stream_len, uint32_t n_streams, const lora_hip_link_request_t *req, size_t n,
+                                             lora_hip_link_metrics_t *metrics_out, lora_hip_link_window_t *windows_out, void *hip_stream)
+{
+    if (!h || !d_iq || !n_streams || !stream_off || !stream_len || (n && (!req || !metrics_out))) return LORA_HIP_ERR_ARG;
+    if (h->pass_open) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_link_measure_device: a pass is open on this handle");
+    for (uint32_t s = 0; s < n_streams; s++)
+        if (stream_off[s] > total_items || stream_len[s] > total_items - stream_off[s]) return fail(h, LORA_HIP_ERR_ARG, "stream %u exceeds the buffer", s);
+    std::vector<LinkReq> rq(n);
+    for (size_t i = 0; i < n; i++) {
+        if (req[i].stream >= n_streams) return fail(h, LORA_HIP_ERR_ARG, "request %zu: bad stream", i);
+        rq[i] = LinkReq{stream_off[req[i].stream], stream_len[req[i].stream], req[i].header_pos};
+    }
+    if (n == 0) return LORA_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->err.clear();
+    return link_run(h, (const float2 *)d_iq, rq.data(), n, metrics_out, windows_out, (hipStream_t)hip_stream);
+}
+
+lora_hip_status lora_hip_link_enable(lora_hip_decoder_t *h, int on)
+{
+    if (!h) return LORA_HIP_ERR_ARG;
+    h->link.on = on != 0;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_link_poll_frame(lora_hip_decoder_t *h, uint8_t *buf, size_t cap, size_t *len, lora_hip_frame_info_t *info, lora_hip_link_metrics_t *metrics)
+{
+    if (!h || !len || !metrics) return LORA_HIP_ERR_ARG;
+    if (h->frames.empty()) { *len = 0; return LORA_HIP_OK; }
+    const lora_hip_link_metrics_t m = h->frames.front().link;
+    const lora_hip_status s = lora_hip_poll_frame(h, buf, cap, len, info);
+    if (s == LORA_HIP_OK) *metrics = m;
+    return s;
+}
+
+lora_hip_status lora_hip_link_drain_frames(lora_hip_decoder_t *h, uint8_t *buf, size_t cap, lora_hip_frame_info_t *infos, lora_hip_link_metrics_t *metrics,
+                                           size_t max_frames, size_t *n_frames)
+{
+    if (!h || !n_frames || (max_frames && (!buf || !infos || !metrics))) return LORA_HIP_ERR_ARG;
+    size_t n = 0, used = 0;
+    while (n < max_frames && !h->frames.empty()) {
+        const FrameQueue::Ref &f = h->frames.front();
+        if (used + f.info.length > cap) break;
+        std::memcpy(buf + used, h->frames.front_bytes(), f.info.length);
+        infos[n] = f.info;
+        metrics[n] = f.link;
+        used += f.info.length;
+        n++;
+        h->frames.pop();
+    }
+    *n_frames = n;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_link_mux_enable(lora_hip_mux_t *m, int on) { return m ? lora_hip_link_enable(m->h, on) : LORA_HIP_ERR_ARG; }
+
+lora_hip_status lora_hip_link_mux_poll_frame(lora_hip_mux_t *m, uint8_t *buf, size_t cap, size_t *len, lora_hip_frame_info_t *info, lora_hip_link_metrics_t *metrics)
+{
+    return m ? lora_hip_link_poll_frame(m->h, buf, cap, len, info, metrics) : LORA_HIP_ERR_ARG;
+}
+
+lora_hip_status lora_hip_link_stats(const lora_hip_decoder_t *h, uint64_t *launches, uint64_t *frames, double *kernel_ms)
+{
+    if (!h) return LORA_HIP_ERR_ARG;
+    if (launches) *launches = h->link.launches;
+    if (frames) *frames = h->link.frames;
+    if (kernel_ms) *kernel_ms = h->link.kernel_ms;
+    return LORA_HIP_OK;
 }
 
 } // extern "C"

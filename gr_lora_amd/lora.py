@@ -91,6 +91,15 @@ def _hex_line(data: bytes, endline: bool, ascii_part: bool) -> str:
     return s + ("\n" if endline else "")
 
 
+def _link_message(blob, info, metrics, **where) -> dict:
+    """What the "link" port carries for one frame: the metrics of include/lora_hip_link.h, the frame's blob and header position,
+    and where it came from (the gateways: row, grid_index, sf, freq_hz)."""
+    d = metrics.as_dict()
+    d.update(blob=blob, header_pos=int(info.header_pos), end_pos=int(info.end_pos))
+    d.update(where)
+    return d
+
+
 class decoder(_MsgBlock):
     """gr::lora::decoder on the MI355X.  demod: capi.DEMOD_FFT_COMPAT (default; dechirp x FFT x
     argmax, byte-identical to the upstream default path's bin convention), DEMOD_FFT, or
@@ -98,8 +107,10 @@ class decoder(_MsgBlock):
 
     def __init__(self, samp_rate, bandwidth, sf, implicit, cr, crc, reduced_rate=False,
                  disable_drift_correction=False, *, device=0, demod=capi.DEMOD_FFT_COMPAT, verbose=True,
-                 batch_items=0, segment_symbols=0, cfo_estimates=False):
+                 batch_items=0, segment_symbols=0, cfo_estimates=False, link_metrics=False):
         super().__init__()
+        self._link = bool(link_metrics)                # each "frames" message is followed by its metrics on "link" (include/lora_hip_link.h)
+        self._where = dict(sf=int(sf), bandwidth=int(bandwidth), row_rate=float(samp_rate))
         self._cfo = bool(cfo_estimates)
         self._hist = None                              # cfo_estimates: ring buffer of the most recent input, for the preamble windows
         self._hist_end = 0                             # absolute item index one past the newest item in the ring
@@ -136,6 +147,9 @@ class decoder(_MsgBlock):
             self._hist = np.zeros(2 * eff_batch + longest + 8 * self._h.sps, dtype=np.complex64)
         self.message_port_register_out("frames")    # decoder_impl.cc:120
         self.message_port_register_out("control")   # :121 (registered, never published upstream)
+        self.message_port_register_out("link")
+        if self._link:
+            self._h.enable_link(True)
 
     # scheduler-facing ------------------------------------------------------
     def output_multiple(self) -> int:
@@ -167,11 +181,13 @@ class decoder(_MsgBlock):
         self._publish()
 
     def _publish(self):
-        for blob, _info in self._h.drain():
+        for blob, _info, *met in (self._h.drain_link() if self._link else self._h.drain()):
             if self._verbose:  # :832 and :872
                 sys.stdout.write(_hex_line(blob[LORATAP_LEN:LORATAP_LEN + LORAPHY_LEN], False, False))
                 sys.stdout.write(_hex_line(blob[LORATAP_LEN + LORAPHY_LEN:], True, True))
             self.message_port_pub("frames", blob)
+            if self._link:
+                self.message_port_pub("link", _link_message(blob, _info, met[0], **self._where))
             if self._cfo:
                 self._publish_cfo(_info)
 
@@ -297,8 +313,10 @@ class gateway_receiver(_MsgBlock):
     "channel_frames"; per channel the frames are what lora_receiver on that channel alone publishes from the same channel samples."""
 
     def __init__(self, samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sf, implicit, cr, crc, decimation=1,
-                 reduced_rate=False, disable_drift_correction=False, device=0, demod=capi.DEMOD_FFT_COMPAT, batch_items=0, latency_ms=None):
+                 reduced_rate=False, disable_drift_correction=False, device=0, demod=capi.DEMOD_FFT_COMPAT, batch_items=0, latency_ms=None,
+                 link_metrics=False):
         super().__init__()
+        self._link = bool(link_metrics)
         self.samp_rate = samp_rate
         self.center_freq = center_freq
         self.channels = [int(k) for k in channels]
@@ -316,6 +334,9 @@ class gateway_receiver(_MsgBlock):
             self.mux.set_latency(float(latency_ms))
         self.message_port_register_out("frames")
         self.message_port_register_out("channel_frames")
+        self.message_port_register_out("link")
+        if self._link:
+            self.mux.enable_link(True)
 
     def work(self, input_items, scale=0) -> int:
         raw = _integer_iq(input_items, scale)
@@ -335,9 +356,14 @@ class gateway_receiver(_MsgBlock):
         self._publish()
 
     def _publish(self):
-        for blob, info in self.mux.drain():
+        for blob, info, *met in (self.mux.drain_link() if self._link else self.mux.drain()):
             self.message_port_pub("frames", blob)
             self.message_port_pub("channel_frames", (self.channels[info.stream], blob))
+            if self._link:
+                k = self.channels[info.stream]
+                self.message_port_pub("link", _link_message(blob, info, met[0], row=int(info.stream), grid_index=k, sf=int(self.sf),
+                                                            freq_hz=self.filterbank.channel_freq(k), bandwidth=self.filterbank.bandwidth,
+                                                            row_rate=float(self.samp_rate) / self.decimation))
 
     def close(self):
         self.mux.close()
@@ -357,8 +383,11 @@ class multi_sf_gateway_receiver(_MsgBlock):
     reduced_rate: None = LoRaWAN's rule per SF (lorawan_reduced_rate), a bool for every SF, or a dict {sf: bool}."""
 
     def __init__(self, samp_rate, center_freq, grid_offset, n_grid, channels, bandwidth, sfs=(7, 8, 9, 10, 11, 12), implicit=False, cr=4,
-                 crc=True, reduced_rate=None, decimation=1, device=0, demod=capi.DEMOD_FFT_COMPAT, latency_ms=None):
+                 crc=True, reduced_rate=None, decimation=1, device=0, demod=capi.DEMOD_FFT_COMPAT, latency_ms=None, link_metrics=False):
         super().__init__()
+        self._link = bool(link_metrics)
+        self._grid = (float(center_freq) + float(grid_offset), float(samp_rate) / int(n_grid))   # frequency of grid channel 0, channel spacing
+        self.bandwidth = int(bandwidth)
         self.samp_rate = samp_rate
         self.center_freq = center_freq
         self.channels = [int(k) for k in channels]
@@ -386,6 +415,9 @@ class multi_sf_gateway_receiver(_MsgBlock):
         self.message_port_register_out("frames")
         self.message_port_register_out("channel_frames")
         self.message_port_register_out("sf_frames")
+        self.message_port_register_out("link")
+        if self._link:
+            self.gateway.enable_link(True)
 
     def work(self, input_items, scale=0) -> int:
         """numpy complex64 (host), or a torch CUDA tensor (complex64, or float32 interleaved) read on the current stream; or integer
@@ -434,10 +466,14 @@ class multi_sf_gateway_receiver(_MsgBlock):
         return self.gateway.stats()
 
     def _publish(self):
-        for blob, info in self.gateway.drain():
+        for blob, info, *met in (self.gateway.drain_link() if self._link else self.gateway.drain()):
             self.message_port_pub("frames", blob)
             self.message_port_pub("channel_frames", (info.grid_index, blob))
             self.message_port_pub("sf_frames", (info.grid_index, info.sf, blob))
+            if self._link:
+                self.message_port_pub("link", _link_message(blob, info, met[0], row=int(info.row), grid_index=int(info.grid_index), sf=int(info.sf),
+                                                            freq_hz=self._grid[0] + self._grid[1] * int(info.grid_index), bandwidth=self.bandwidth,
+                                                            row_rate=float(self.samp_rate) / self.decimation))
 
     def close(self):
         self.gateway.close()
@@ -639,6 +675,33 @@ class message_socket_sink(_MsgBlock):
             end = len(blob) - (MAC_CRC_SIZE if has_mac_crc else 0)
             data = blob[LORATAP_LEN + LORAPHY_LEN:end]
         self._sock.sendto(data, self.addr)
+
+    def close(self):
+        self._sock.close()
+
+
+class packet_forwarder_sink(_MsgBlock):
+    """"link" messages -> Semtech UDP packet-forwarder PUSH_DATA datagrams (gr_lora_amd/forwarder.py), one per message.  A message
+    that carries no freq_hz (lora.decoder's) is reported at the `freq_hz` given here."""
+
+    def __init__(self, host, port, gateway_eui, rssi_offset_db=0.0, freq_hz=0.0):
+        super().__init__()
+        from . import forwarder
+        self._fw = forwarder
+        self.addr = (host, int(port))
+        self.eui = forwarder.eui_bytes(gateway_eui)
+        self.rssi_offset_db = float(rssi_offset_db)
+        self.freq_hz = float(freq_hz)
+        self.sent = 0
+        self._sock = socket.socket(socket.AF_INET, socket.SOCK_DGRAM)
+        self.message_port_register_in("link", self.handle)
+        self.message_port_register_in("in", self.handle)
+
+    def handle(self, link: dict):
+        pk = self._fw.rxpk(link["blob"], link, freq_hz=link.get("freq_hz", self.freq_hz), sf=link["sf"], bandwidth=link["bandwidth"],
+                           row_rate=link["row_rate"], rssi_offset_db=self.rssi_offset_db)
+        self._sock.sendto(self._fw.push_data(self.eui, [pk]), self.addr)
+        self.sent += 1
 
     def close(self):
         self._sock.close()

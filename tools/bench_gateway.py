@@ -3,6 +3,7 @@ tools/bench_filterbank.py with mixed-SF traffic, against six single-SF gateway_r
 workload.
 
     python tools/bench_gateway.py [--workload a|b] [--runs R] [--out profiles/gateway_bench_lines.jsonl] [--no-baseline]
+    python tools/bench_gateway.py --link [--workload a|b] [--runs R]      # link metrics off against on
 
 Workloads (one wide-band capture -> every grid channel at 1 Msps -> SF7..SF12 decoders on every channel):
     a  EU868-like:  fs 2 Msps,  M 10, D 2,  8 channels, 2-3 frames per channel at different SFs
@@ -199,10 +200,10 @@ def cached(key):
     return wide, expect
 
 
-def run_gateway(w, d_wide, n):
+def run_gateway(w, d_wide, n, link=False):
     import torch
     from gr_lora_amd import lora
-    rx = lora.multi_sf_gateway_receiver(w["fs"], 0.0, w["f0"], w["M"], w["ks"], 125000, sfs=SFS, decimation=w["D"])
+    rx = lora.multi_sf_gateway_receiver(w["fs"], 0.0, w["f0"], w["M"], w["ks"], 125000, sfs=SFS, decimation=w["D"], link_metrics=link)
     frames = []
     rx.subscribe("sf_frames", frames.append)
     torch.cuda.synchronize()
@@ -326,6 +327,30 @@ def measure(key, runs, baseline):
     return line
 
 
+def measure_link(key, runs):
+    """The gateway with link metrics (include/lora_hip_link.h) off and on, runs interleaved in one process."""
+    import torch
+    w = WORKLOADS[key]
+    wide, expect = cached(key)
+    n = wide.size
+    d_wide = torch.from_numpy(wide).to("cuda:0")
+    for link in (False, True):
+        run_gateway(w, d_wide, n, link)                # warm-up
+    dts = {False: [], True: []}
+    frames = {}
+    for _ in range(runs):
+        for link in (False, True):
+            dt, fr, _ = run_gateway(w, d_wide, n, link)
+            dts[link].append(dt)
+            frames[link] = fr
+    off, on = float(np.median(dts[False])), float(np.median(dts[True]))
+    return dict(bench="gateway_link", workload=key, name=w["name"], items=n, frames_published=len(frames[True]),
+                frames_equal=[(int(k), int(sf), b) for k, sf, b in frames[False]] == [(int(k), int(sf), b) for k, sf, b in frames[True]],
+                link_off_s=round(off, 4), link_off_runs_s=[round(x, 4) for x in dts[False]], link_off_items_per_s=round(n / off, 1),
+                link_on_s=round(on, 4), link_on_runs_s=[round(x, 4) for x in dts[True]], link_on_items_per_s=round(n / on, 1),
+                link_on_over_off=round(on / off, 4))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--workload", choices=sorted(WORKLOADS), action="append")
@@ -335,11 +360,14 @@ def main():
     ap.add_argument("--format", choices=["sc16", "sc8", "cu8"], help="the host-ingest comparison: integers against complex64, both from host memory")
     ap.add_argument("--device-synth", action="store_true", help="synthesise the capture on the device (lora.traffic_synthesizer) and feed work_device from HBM")
     ap.add_argument("--seconds", type=float, help="with --device-synth: seconds of air (default: the default path's plan, frame for frame)")
+    ap.add_argument("--link", action="store_true", help="throughput with link metrics off and on (interleaved runs)")
     a = ap.parse_args()
     if a.seconds is not None and not a.device_synth:
         ap.error("--seconds goes with --device-synth")
     for key in a.workload or sorted(WORKLOADS):
-        if a.device_synth:
+        if a.link:
+            line = json.dumps(measure_link(key, a.runs))
+        elif a.device_synth:
             line = json.dumps(measure_device_synth(key, a.runs, a.seconds))
         else:
             line = json.dumps(measure_host_ingest(key, a.runs, a.format) if a.format else measure(key, a.runs, not a.no_baseline))
