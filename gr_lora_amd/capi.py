@@ -66,7 +66,15 @@ EXPORTS_LINK = [
     "lora_hip_link_stats",
 ]
 
+EXPORTS_SPECTRUM = [
+    "lora_hip_spectrum_create", "lora_hip_spectrum_destroy", "lora_hip_spectrum_last_error", "lora_hip_spectrum_window",
+    "lora_hip_spectrum_output_rows", "lora_hip_spectrum_run_device", "lora_hip_spectrum_run_device_raw", "lora_hip_spectrum_work",
+    "lora_hip_spectrum_work_raw", "lora_hip_spectrum_reset", "lora_hip_spectrum_last_kernel_ms",
+]
+
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
+SPECTRUM_WINDOW_HANN, SPECTRUM_WINDOW_RECT = 0, 1   # include/lora_hip_spectrum.h
+SPECTRUM_FLAG_PEAK = 1
 GATEWAY_MAX_DECODERS = 7      # include/lora_hip_gateway.h
 GATEWAY_STEP_OUTPUTS = 65536  # include/lora_hip_gateway.h
 
@@ -75,6 +83,11 @@ class FilterBankConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("samp_rate", C.c_double), ("grid_offset_hz", C.c_double), ("n_grid", C.c_uint32),
                 ("channels", C.POINTER(C.c_int32)), ("n_channels", C.c_uint32), ("bandwidth", C.c_uint32), ("decimation", C.c_uint32),
                 ("device", C.c_int32), ("cutoff_hz", C.c_float), ("transition_hz", C.c_float), ("flags", C.c_uint32)]
+
+
+class SpectrumConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("samp_rate", C.c_double), ("nfft", C.c_uint32), ("hop", C.c_uint32), ("n_avg", C.c_uint32),
+                ("window", C.c_uint32), ("flags", C.c_uint32), ("bands", C.POINTER(C.c_uint32)), ("n_bands", C.c_uint32), ("device", C.c_int32)]
 
 
 class ChannelizerConfig(C.Structure):
@@ -356,6 +369,23 @@ def load():
         L.lora_hip_link_gateway_enable.argtypes = [vp, C.c_int]
         L.lora_hip_link_gateway_poll_frame.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(GatewayFrameInfo), C.POINTER(LinkMetrics)]
         L.lora_hip_link_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+    if hasattr(L, "lora_hip_spectrum_create") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        u64p, szp = C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.lora_hip_spectrum_create.argtypes = [C.POINTER(SpectrumConfig), C.POINTER(vp)]
+        L.lora_hip_spectrum_destroy.argtypes = [vp]
+        L.lora_hip_spectrum_destroy.restype = None
+        L.lora_hip_spectrum_last_error.argtypes = [vp]
+        L.lora_hip_spectrum_last_error.restype = C.c_char_p
+        L.lora_hip_spectrum_window.argtypes = [vp, vp, C.c_size_t, szp]
+        L.lora_hip_spectrum_output_rows.argtypes = [vp, C.c_size_t]
+        L.lora_hip_spectrum_output_rows.restype = C.c_size_t
+        L.lora_hip_spectrum_run_device.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_spectrum_run_device_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, vp, vp, C.c_size_t, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_spectrum_work.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.c_size_t, szp, u64p]
+        L.lora_hip_spectrum_work_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, vp, vp, C.c_size_t, C.c_size_t, szp, u64p]
+        L.lora_hip_spectrum_reset.argtypes = [vp]
+        L.lora_hip_spectrum_last_kernel_ms.argtypes = [vp]
+        L.lora_hip_spectrum_last_kernel_ms.restype = C.c_float
     _lib = L
     return L
 
@@ -914,6 +944,102 @@ class FilterBank:
     def close(self):
         if self.h:
             self.L.lora_hip_filterbank_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Spectrum:
+    """lora_hip_spectrum_* (include/lora_hip_spectrum.h): Welch power-spectrum rows and band powers of a wide-band capture.
+    bands: (first_bin, n_bins) pairs in centred indices (gr_lora_amd.spectrum.band_bins / grid_bands make them)."""
+
+    def __init__(self, samp_rate, nfft=1024, hop=512, n_avg=16, window=SPECTRUM_WINDOW_HANN, peak=False, bands=(), device=0):
+        self.L = load()
+        self.nfft, self.hop, self.n_avg = int(nfft), int(hop), int(n_avg)
+        self.bands = [(int(a), int(b)) for a, b in bands]
+        self.n_bands = len(self.bands)
+        self.peak = bool(peak)
+        self._bands = (C.c_uint32 * max(2 * self.n_bands, 1))(*[v for b in self.bands for v in b])
+        cfg = SpectrumConfig(struct_size=C.sizeof(SpectrumConfig), samp_rate=float(samp_rate), nfft=self.nfft, hop=self.hop, n_avg=self.n_avg,
+                             window=int(window), flags=SPECTRUM_FLAG_PEAK if peak else 0,
+                             bands=self._bands, n_bands=self.n_bands, device=int(device))
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_spectrum_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            raise LoraHipError(st, self.L.lora_hip_strerror(st).decode())
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, (self.L.lora_hip_spectrum_last_error(self.h) or b"").decode() or self.L.lora_hip_strerror(st).decode())
+
+    def window(self) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_spectrum_window(self.h, None, 0, C.byref(n)))
+        w = np.zeros(n.value, dtype=np.float32)
+        self._check(self.L.lora_hip_spectrum_window(self.h, w.ctypes.data, w.size, C.byref(n)))
+        return w
+
+    def output_rows(self, n_in: int) -> int:
+        return int(self.L.lora_hip_spectrum_output_rows(self.h, int(n_in)))
+
+    def _host_out(self, rows):
+        r = max(rows, 1)
+        psd = np.zeros((r, self.nfft), dtype=np.float32)
+        peak = np.zeros((r, self.nfft), dtype=np.float32) if self.peak else None
+        band = np.zeros((r, self.n_bands), dtype=np.float32) if self.n_bands else None
+        return psd, peak, band
+
+    @staticmethod
+    def _cut(psd, peak, band, n, first):
+        return psd[:n], (None if peak is None else peak[:n]), (None if band is None else band[:n]), int(first)
+
+    def work(self, x, max_rows=None):
+        """Host buffers: complex64[n_in] -> (psd[rows, nfft], peak or None, band[rows, n_bands] or None, first_row), float32."""
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        rows = self.output_rows(a.size) if max_rows is None else int(max_rows)
+        psd, peak, band = self._host_out(rows)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_spectrum_work(self.h, a.ctypes.data, a.size, psd.ctypes.data, None if peak is None else peak.ctypes.data,
+                                                  None if band is None else band.ctypes.data, self.nfft, rows, C.byref(n), C.byref(first)))
+        return self._cut(psd, peak, band, n.value, first.value)
+
+    def work_raw(self, raw, fmt=None, scale: float = 0.0, max_rows=None):
+        """Integer items in (flat interleaved or (n, 2); fmt None: from the dtype); output as work()."""
+        a, f, n_items = _raw_items(raw, fmt)
+        rows = self.output_rows(n_items) if max_rows is None else int(max_rows)
+        psd, peak, band = self._host_out(rows)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_spectrum_work_raw(self.h, a.ctypes.data, n_items, f, float(scale), psd.ctypes.data,
+                                                      None if peak is None else peak.ctypes.data, None if band is None else band.ctypes.data,
+                                                      self.nfft, rows, C.byref(n), C.byref(first)))
+        return self._cut(psd, peak, band, n.value, first.value)
+
+    def run_device(self, d_in: int, n_in: int, d_psd: int, d_peak, d_band, row_stride: int, max_rows: int, stream: int = 0):
+        """-> (rows written, absolute index of the first of them); d_peak / d_band None where the handle has none."""
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_spectrum_run_device(self.h, d_in, int(n_in), d_psd, d_peak, d_band, int(row_stride), int(max_rows), C.byref(n),
+                                                        C.byref(first), stream))
+        return int(n.value), int(first.value)
+
+    def run_device_raw(self, d_in: int, n_in: int, fmt: int, d_psd: int, d_peak, d_band, row_stride: int, max_rows: int, scale: float = 0.0, stream: int = 0):
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_spectrum_run_device_raw(self.h, d_in, int(n_in), int(fmt), float(scale), d_psd, d_peak, d_band, int(row_stride),
+                                                            int(max_rows), C.byref(n), C.byref(first), stream))
+        return int(n.value), int(first.value)
+
+    def reset(self):
+        self._check(self.L.lora_hip_spectrum_reset(self.h))
+
+    def kernel_ms(self) -> float:
+        return float(self.L.lora_hip_spectrum_last_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.lora_hip_spectrum_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

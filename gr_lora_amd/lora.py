@@ -14,6 +14,9 @@ Same names, argument order and meaning as the reference module `lora`:
   lora.modulator(samp_rate, bandwidth, sf, implicit, cr, crc, reduced_rate)
                                               (not upstream, which only receives: the decoder's mirror, one frame per call)
   lora.traffic_synthesizer(samp_rate, ...)    (not upstream: a wide-band capture of many concurrent emitters, made on the device)
+  lora.spectrum_scanner(samp_rate, nfft, hop, n_avg, window, peak, bands)
+                                              (not upstream: Welch power-spectrum rows and per-channel band powers of the capture,
+                                              on the device, beside the receivers and fed the same array)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -531,6 +534,103 @@ class traffic_synthesizer:
     @property
     def pending(self) -> int:
         return self._h.pending
+
+    def kernel_ms(self) -> float:
+        return self._h.kernel_ms()
+
+    def close(self):
+        self._h.close()
+
+
+class spectrum_record:
+    """What spectrum_scanner.work returns: psd[rows, nfft] (full-scale^2 per bin, centred: index nfft / 2 is DC), peak[rows, nfft] or
+    None, band[rows, n_bands] or None (float32 numpy), first_sample[rows] (absolute index of each row's first sample) and
+    freqs[nfft] (Hz from the capture's centre)."""
+
+    def __init__(self, psd, peak, band, first_sample, freqs):
+        self.psd, self.peak, self.band, self.first_sample, self.freqs = psd, peak, band, first_sample, freqs
+
+    def __len__(self):
+        return int(self.psd.shape[0])
+
+
+class spectrum_scanner:
+    """The spectral scan (include/lora_hip_spectrum.h, csrc/lora_spectrum.hip): Welch rows of the capture's power spectrum and
+    the power in each band, computed on the device in one pass.  Feed it what multi_sf_gateway_receiver.work is fed, in any
+    chunking: the rows are the same.  gr_lora_amd.spectrum.welch_rows is the definition.  hop None: nfft // 2.  bands: (f_lo, f_hi)
+    pairs in Hz from the capture's centre (a bin belongs to a band when its centre lies in [f_lo, f_hi)).  No host fall-back."""
+
+    def __init__(self, samp_rate, nfft=1024, hop=None, n_avg=16, window="hann", peak=False, bands=None, device=0, _bins=None):
+        from . import spectrum
+        self.samp_rate = float(samp_rate)
+        self.nfft = int(nfft)
+        self.hop = self.nfft // 2 if hop is None else int(hop)
+        self.n_avg = int(n_avg)
+        self.device = int(device)
+        self.bands = [(float(lo), float(hi)) for lo, hi in (bands or [])]
+        self.band_bins = list(_bins) if _bins is not None else [spectrum.band_bins(self.samp_rate, self.nfft, lo, hi) for lo, hi in self.bands]
+        self.freqs = spectrum.freqs(self.samp_rate, self.nfft)
+        self._h = capi.Spectrum(self.samp_rate, self.nfft, self.hop, self.n_avg, spectrum.window_id(window), bool(peak), self.band_bins, self.device)
+        self.window = self._h.window()
+
+    @classmethod
+    def for_grid(cls, samp_rate, grid_offset, n_grid, channels, bandwidth, nfft=1024, hop=None, n_avg=16, window="hann", peak=False, device=0):
+        """One band per filter-bank channel (spectrum.grid_bands): band c is grid_offset + channels[c] * samp_rate / n_grid, +- bandwidth / 2."""
+        from . import spectrum
+        bins = spectrum.grid_bands(samp_rate, nfft, grid_offset, n_grid, channels, bandwidth)
+        f = [float(grid_offset) + int(k) * float(samp_rate) / int(n_grid) for k in channels]
+        return cls(samp_rate, nfft, hop, n_avg, window, peak, [(x - bandwidth / 2.0, x + bandwidth / 2.0) for x in f], device, _bins=bins)
+
+    def _record(self, psd, peak, band, first_row):
+        first = (int(first_row) + np.arange(psd.shape[0], dtype=np.int64)) * (self.n_avg * self.hop)
+        return spectrum_record(psd, peak, band, first, self.freqs)
+
+    def work(self, x, scale=0) -> spectrum_record:
+        """numpy complex64 (host), or a torch CUDA tensor (complex64, or float32 interleaved) read on the current stream; or integer
+        IQ: a numpy array or a torch CUDA tensor of dtype int16 / int8 / uint8, flat interleaved or (n, 2), with an optional scale."""
+        if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            t = x.contiguous()
+            if t.device.index != self.device:
+                raise ValueError("spectrum_scanner.work: the tensor is on %s, the scanner on cuda:%d" % (t.device, self.device))
+            fmt = {torch.int16: iqformat.SC16, torch.int8: iqformat.SC8, torch.uint8: iqformat.CU8}.get(t.dtype)
+            if fmt is not None:
+                if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 2)) or t.numel() % 2:
+                    raise ValueError("spectrum_scanner.work: integer IQ must be flat interleaved pairs or shaped (n, 2), not %s" % (tuple(t.shape),))
+                n = t.numel() // 2
+                sc = iqformat.check_scale(scale)
+            else:
+                if scale:
+                    raise TypeError("spectrum_scanner.work: scale applies to integer IQ, not to %s" % t.dtype)
+                if t.dtype == torch.complex64:
+                    n = t.numel()
+                elif t.dtype == torch.float32:
+                    if t.numel() % 2:
+                        raise ValueError("spectrum_scanner.work: a float32 tensor holds interleaved I/Q pairs, not %d floats" % t.numel())
+                    n = t.numel() // 2
+                else:
+                    raise TypeError("spectrum_scanner.work: a device tensor must be complex64 or float32 interleaved, not %s" % t.dtype)
+            rows = self._h.output_rows(n)
+            r = max(rows, 1)
+            psd = torch.empty((r, self.nfft), dtype=torch.float32, device=t.device)
+            peak = torch.empty((r, self.nfft), dtype=torch.float32, device=t.device) if self._h.peak else None
+            band = torch.empty((r, self._h.n_bands), dtype=torch.float32, device=t.device) if self._h.n_bands else None
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            ptrs = (psd.data_ptr(), None if peak is None else peak.data_ptr(), None if band is None else band.data_ptr())
+            if fmt is not None:
+                got, first = self._h.run_device_raw(t.data_ptr(), n, fmt, *ptrs, self.nfft, rows, sc, stream)
+            else:
+                got, first = self._h.run_device(t.data_ptr(), n, *ptrs, self.nfft, rows, stream)
+            return self._record(psd[:got].cpu().numpy(), None if peak is None else peak[:got].cpu().numpy(),
+                                None if band is None else band[:got].cpu().numpy(), first)
+        raw = _integer_iq(x, scale)
+        if raw is not None:
+            return self._record(*self._h.work_raw(raw[0], raw[1], scale))
+        return self._record(*self._h.work(np.asarray(x, dtype=np.complex64)))
+
+    def reset(self):
+        """Drops the samples and the row in progress: the next item is sample 0."""
+        self._h.reset()
 
     def kernel_ms(self) -> float:
         return self._h.kernel_ms()
