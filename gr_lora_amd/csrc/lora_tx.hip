@@ -74,6 +74,14 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     o0 = c0; o1 = c1;
 }
 
+// x * y rounded once to double.  __dmul_rn is a plain x * y to the compiler, which contracts it into an add or subtract behind it
+// (v_fma_f64: the product is then never rounded); the pragma takes the contract flag off this multiply alone.
+__device__ __forceinline__ double mul_rn(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x * y;
+}
+
 template <int F>
 __device__ __forceinline__ void tx_store(void *out, long long idx, float2 v, double fs)
 {
@@ -82,7 +90,7 @@ __device__ __forceinline__ void tx_store(void *out, long long idx, float2 v, dou
     } else {
         constexpr double lo = F == LORA_HIP_IQ_SC16 ? -32768.0 : F == LORA_HIP_IQ_SC8 ? -128.0 : 0.0;
         constexpr double hi = F == LORA_HIP_IQ_SC16 ? 32767.0 : F == LORA_HIP_IQ_SC8 ? 127.0 : 255.0;
-        double a = __dmul_rn((double)v.x, fs), b = __dmul_rn((double)v.y, fs);
+        double a = mul_rn((double)v.x, fs), b = mul_rn((double)v.y, fs);
         if constexpr (F == LORA_HIP_IQ_CU8) { a = __dadd_rn(a, 127.5); b = __dadd_rn(b, 127.5); }
         const int ia = (int)fmin(fmax(rint(a), lo), hi), ib = (int)fmin(fmax(rint(b), lo), hi);
         if constexpr (F == LORA_HIP_IQ_SC16)
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void tx_kernel(TxArgs a)
             const double num = (double)i * (double)(i - d.sps);      // exact, |num| <= 2^42
             const double rem = fma(-rint(num * d.inv_den), d.den, num); // num mod den, exact, in [-den/2, den/2]
             const double tc = down ? -(rem * d.inv_den) : rem * d.inv_den;
-            const double x = __dmul_rn(d.tps, (double)(p + d.start));
+            const double x = mul_rn(d.tps, (double)(p + d.start));
             double t = (x - floor(x)) + tc;
             t -= rint(t);
             const float th = (float)t, tl = (float)(t - (double)th);
