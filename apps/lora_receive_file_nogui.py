@@ -2,7 +2,8 @@
 """GNU-Radio-free equivalent of the reference's apps/lora_receive_file_nogui.py:
 SigMF trace -> lora_receiver (channeliser + MI355X decoder) -> message_socket_sink (UDP).
 The capture is fed in its own datatype: cf32_le as complex64, ci16_le / ci8 / cu8 as the integers in the file, which the
-channeliser converts on the device (gr_lora_amd/iqformat.py)."""
+channeliser converts on the device (gr_lora_amd/iqformat.py).  --resample-to HZ puts a rational_resampler in front of the receiver for
+a capture whose rate is no multiple of the bandwidth (2.4 Msps from an RTL-SDR: --resample-to 1000000)."""
 import argparse
 import os
 import sys
@@ -18,13 +19,16 @@ def main(argv=None):
     ap.add_argument("--ip", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=40868)
     ap.add_argument("--chunk", type=int, default=1 << 16, help="items per work() call")
+    ap.add_argument("--resample-to", type=float, default=None, metavar="HZ",
+                    help="resample the capture to this rate on the device before the receiver (HZ / sample_rate must be L / M with L, M <= 512)")
     args = ap.parse_args(argv)
     meta = sigmf.read_meta(args.file + ".sigmf-meta")
     cfg = sigmf.LoRaConfig(meta["transmit_freq"], meta["sf"], meta["cr"], meta["bw"], meta["prlen"], meta["crc"], meta["implicit"])
     print("[+] Configuration: %s" % cfg.string_repr())
     print("[+] Decoding. You should see a header, followed by '%s'%s %d times." % (
         meta["expected"], " and a CRC" if meta["crc"] else "", meta["times"]))
-    rx = lora.lora_receiver(meta["sample_rate"], meta["capture_freq"], [meta["transmit_freq"]], cfg.bw, cfg.sf,
+    resampler = lora.rational_resampler(meta["sample_rate"], args.resample_to) if args.resample_to else None
+    rx = lora.lora_receiver(args.resample_to if resampler else meta["sample_rate"], meta["capture_freq"], [meta["transmit_freq"]], cfg.bw, cfg.sf,
                             cfg.implicit, cfg.cr_num, cfg.crc)
     sink = lora.message_socket_sink(args.ip, args.port, 0)
     lora.msg_connect(rx, "frames", sink, "in")
@@ -32,8 +36,10 @@ def main(argv=None):
     iq = sigmf.read_data(args.file + ".sigmf-data", datatype)
     step = args.chunk * (1 if datatype == "cf32_le" else 2)   # (integer captures: two components per item)
     for i in range(0, iq.size, step):
-        rx.work(iq[i:i + step])
+        rx.work(resampler.work(iq[i:i + step]) if resampler else iq[i:i + step])
     rx.stop()
+    if resampler:
+        resampler.close()
     rx.decoder.close()
     if rx.channelizer is not None:
         rx.channelizer._h.close()

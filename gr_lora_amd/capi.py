@@ -72,6 +72,13 @@ EXPORTS_SPECTRUM = [
     "lora_hip_spectrum_work_raw", "lora_hip_spectrum_reset", "lora_hip_spectrum_last_kernel_ms",
 ]
 
+EXPORTS_RESAMPLER = [
+    "lora_hip_resampler_create", "lora_hip_resampler_destroy", "lora_hip_resampler_last_error", "lora_hip_resampler_taps",
+    "lora_hip_resampler_ratio", "lora_hip_resampler_delay", "lora_hip_resampler_get_plan", "lora_hip_resampler_output_items",
+    "lora_hip_resampler_run_device", "lora_hip_resampler_run_device_raw", "lora_hip_resampler_work", "lora_hip_resampler_work_raw",
+    "lora_hip_resampler_reset", "lora_hip_resampler_last_kernel_ms",
+]
+
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
 SPECTRUM_WINDOW_HANN, SPECTRUM_WINDOW_RECT = 0, 1   # include/lora_hip_spectrum.h
 SPECTRUM_FLAG_PEAK = 1
@@ -88,6 +95,11 @@ class FilterBankConfig(C.Structure):
 class SpectrumConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("samp_rate", C.c_double), ("nfft", C.c_uint32), ("hop", C.c_uint32), ("n_avg", C.c_uint32),
                 ("window", C.c_uint32), ("flags", C.c_uint32), ("bands", C.POINTER(C.c_uint32)), ("n_bands", C.c_uint32), ("device", C.c_int32)]
+
+
+class ResamplerConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("interpolation", C.c_uint32), ("decimation", C.c_uint32), ("zero_crossings", C.c_uint32),
+                ("beta", C.c_double), ("cutoff", C.c_double), ("device", C.c_int32), ("flags", C.c_uint32)]
 
 
 class ChannelizerConfig(C.Structure):
@@ -386,6 +398,27 @@ def load():
         L.lora_hip_spectrum_reset.argtypes = [vp]
         L.lora_hip_spectrum_last_kernel_ms.argtypes = [vp]
         L.lora_hip_spectrum_last_kernel_ms.restype = C.c_float
+    if hasattr(L, "lora_hip_resampler_create") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        u32p, u64p, szp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.lora_hip_resampler_create.argtypes = [C.POINTER(ResamplerConfig), C.POINTER(vp)]
+        L.lora_hip_resampler_destroy.argtypes = [vp]
+        L.lora_hip_resampler_destroy.restype = None
+        L.lora_hip_resampler_last_error.argtypes = [vp]
+        L.lora_hip_resampler_last_error.restype = C.c_char_p
+        L.lora_hip_resampler_taps.argtypes = [vp, vp, C.c_size_t, szp]
+        L.lora_hip_resampler_ratio.argtypes = [vp, u32p, u32p, u32p]
+        L.lora_hip_resampler_delay.argtypes = [vp]
+        L.lora_hip_resampler_delay.restype = C.c_double
+        L.lora_hip_resampler_get_plan.argtypes = [vp, u32p, u32p, u32p, szp]
+        L.lora_hip_resampler_output_items.argtypes = [vp, C.c_size_t]
+        L.lora_hip_resampler_output_items.restype = C.c_size_t
+        L.lora_hip_resampler_run_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_resampler_run_device_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_resampler_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, u64p]
+        L.lora_hip_resampler_work_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, szp, u64p]
+        L.lora_hip_resampler_reset.argtypes = [vp]
+        L.lora_hip_resampler_last_kernel_ms.argtypes = [vp]
+        L.lora_hip_resampler_last_kernel_ms.restype = C.c_float
     _lib = L
     return L
 
@@ -1040,6 +1073,96 @@ class Spectrum:
     def close(self):
         if self.h:
             self.L.lora_hip_spectrum_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler:
+    """lora_hip_resampler_* (include/lora_hip_resampler.h): the stream at rate fs -> the stream at rate fs * interpolation / decimation.
+    gr_lora_amd.resampler.resample is the definition."""
+
+    def __init__(self, interpolation, decimation, zero_crossings=16, beta=8.0, cutoff=0.8, device=0):
+        self.L = load()
+        cfg = ResamplerConfig(struct_size=C.sizeof(ResamplerConfig), interpolation=int(interpolation), decimation=int(decimation),
+                              zero_crossings=int(zero_crossings), beta=float(beta), cutoff=float(cutoff), device=int(device), flags=0)
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_resampler_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            raise LoraHipError(st, self.L.lora_hip_strerror(st).decode())
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, (self.L.lora_hip_resampler_last_error(self.h) or b"").decode() or self.L.lora_hip_strerror(st).decode())
+
+    def taps(self) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_resampler_taps(self.h, None, 0, C.byref(n)))
+        t = np.zeros(n.value, dtype=np.float32)
+        self._check(self.L.lora_hip_resampler_taps(self.h, t.ctypes.data, t.size, C.byref(n)))
+        return t
+
+    def ratio(self) -> Tuple[int, int, int]:
+        """The reduced (interpolation, decimation) and the taps per output Q."""
+        l, m, q = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.lora_hip_resampler_ratio(self.h, C.byref(l), C.byref(m), C.byref(q)))
+        return int(l.value), int(m.value), int(q.value)
+
+    def delay(self) -> float:
+        return float(self.L.lora_hip_resampler_delay(self.h))
+
+    def plan(self) -> Tuple[int, int, int, int]:
+        """The launch plan (lora_hip_resampler_get_plan): tile, tiles_per_group, row_stride, lds_bytes."""
+        t, g, s, lds = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+        self._check(self.L.lora_hip_resampler_get_plan(self.h, C.byref(t), C.byref(g), C.byref(s), C.byref(lds)))
+        return int(t.value), int(g.value), int(s.value), int(lds.value)
+
+    def output_items(self, n_in: int) -> int:
+        return int(self.L.lora_hip_resampler_output_items(self.h, int(n_in)))
+
+    def work(self, x, max_out=None):
+        """Host buffers: complex64[n_in] -> (complex64[n_out], absolute index of the first output)."""
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        cap = self.output_items(a.size) if max_out is None else int(max_out)
+        y = np.zeros(max(cap, 1), dtype=np.complex64)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_resampler_work(self.h, a.ctypes.data, a.size, y.ctypes.data, cap, C.byref(n), C.byref(first)))
+        return y[:n.value], int(first.value)
+
+    def work_raw(self, raw, fmt=None, scale: float = 0.0, max_out=None):
+        """Integer items in (flat interleaved or (n, 2); fmt None: from the dtype); output as work()."""
+        a, f, n_items = _raw_items(raw, fmt)
+        cap = self.output_items(n_items) if max_out is None else int(max_out)
+        y = np.zeros(max(cap, 1), dtype=np.complex64)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_resampler_work_raw(self.h, a.ctypes.data, n_items, f, float(scale), y.ctypes.data, cap, C.byref(n), C.byref(first)))
+        return y[:n.value], int(first.value)
+
+    def run_device(self, d_in: int, n_in: int, d_out: int, max_out: int, stream: int = 0):
+        """-> (outputs written, absolute index of the first of them)."""
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_resampler_run_device(self.h, d_in, int(n_in), d_out, int(max_out), C.byref(n), C.byref(first), stream))
+        return int(n.value), int(first.value)
+
+    def run_device_raw(self, d_in: int, n_in: int, fmt: int, d_out: int, max_out: int, scale: float = 0.0, stream: int = 0):
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_resampler_run_device_raw(self.h, d_in, int(n_in), int(fmt), float(scale), d_out, int(max_out), C.byref(n),
+                                                             C.byref(first), stream))
+        return int(n.value), int(first.value)
+
+    def reset(self):
+        self._check(self.L.lora_hip_resampler_reset(self.h))
+
+    def kernel_ms(self) -> float:
+        return float(self.L.lora_hip_resampler_last_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.lora_hip_resampler_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

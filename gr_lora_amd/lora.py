@@ -17,6 +17,9 @@ Same names, argument order and meaning as the reference module `lora`:
   lora.spectrum_scanner(samp_rate, nfft, hop, n_avg, window, peak, bands)
                                               (not upstream: Welch power-spectrum rows and per-channel band powers of the capture,
                                               on the device, beside the receivers and fed the same array)
+  lora.rational_resampler(in_rate, out_rate, zero_crossings, beta, cutoff)
+                                              (not upstream, which leaves it to a GNU Radio block: rate in_rate -> in_rate * L / M on
+                                              the device, in front of any receiver, for captures at 2.4, 2.048, 1.92 ... Msps)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -630,6 +633,72 @@ class spectrum_scanner:
 
     def reset(self):
         """Drops the samples and the row in progress: the next item is sample 0."""
+        self._h.reset()
+
+    def kernel_ms(self) -> float:
+        return self._h.kernel_ms()
+
+    def close(self):
+        self._h.close()
+
+
+class rational_resampler:
+    """The stage in front of the receivers for a capture whose rate is no multiple of the LoRa bandwidth (include/
+    lora_hip_resampler.h, csrc/lora_resampler.hip): the stream at in_rate -> the stream at out_rate = in_rate * L / M, on the device,
+    in any chunking.  gr_lora_amd.resampler.resample is the definition.  Frame positions reported downstream refer to the
+    resampled stream; `delay` is the filter's group delay in output items.  No host fall-back."""
+
+    def __init__(self, in_rate, out_rate, zero_crossings=16, beta=8.0, cutoff=0.8, device=0):
+        from . import resampler
+        self.in_rate, self.out_rate = float(in_rate), float(out_rate)
+        self.interpolation, self.decimation = resampler.ratio(in_rate, out_rate)
+        self.device = int(device)
+        self._h = capi.Resampler(self.interpolation, self.decimation, zero_crossings, beta, cutoff, self.device)
+        self.delay = self._h.delay()
+
+    def work(self, input_items, scale=0):
+        """numpy complex64 (host), or a torch CUDA tensor (complex64, or float32 interleaved) read on the current stream; or integer
+        IQ: a numpy array or a torch CUDA tensor of dtype int16 / int8 / uint8, flat interleaved or (n, 2), with an optional scale.
+        -> the complex64 outputs these items complete: a numpy array for host input, a CUDA tensor written on the current stream
+        for device input."""
+        x = input_items
+        if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            t = x.contiguous()
+            if t.device.index != self.device:
+                raise ValueError("rational_resampler.work: the tensor is on %s, the resampler on cuda:%d" % (t.device, self.device))
+            fmt = {torch.int16: iqformat.SC16, torch.int8: iqformat.SC8, torch.uint8: iqformat.CU8}.get(t.dtype)
+            if fmt is not None:
+                if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 2)) or t.numel() % 2:
+                    raise ValueError("rational_resampler.work: integer IQ must be flat interleaved pairs or shaped (n, 2), not %s" % (tuple(t.shape),))
+                n = t.numel() // 2
+                sc = iqformat.check_scale(scale)
+            else:
+                if scale:
+                    raise TypeError("rational_resampler.work: scale applies to integer IQ, not to %s" % t.dtype)
+                if t.dtype == torch.complex64:
+                    n = t.numel()
+                elif t.dtype == torch.float32:
+                    if t.numel() % 2:
+                        raise ValueError("rational_resampler.work: a float32 tensor holds interleaved I/Q pairs, not %d floats" % t.numel())
+                    n = t.numel() // 2
+                else:
+                    raise TypeError("rational_resampler.work: a device tensor must be complex64 or float32 interleaved, not %s" % t.dtype)
+            cap = self._h.output_items(n)
+            y = torch.empty(max(cap, 1), dtype=torch.complex64, device=t.device)
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            if fmt is not None:
+                got, _first = self._h.run_device_raw(t.data_ptr(), n, fmt, y.data_ptr(), cap, sc, stream)
+            else:
+                got, _first = self._h.run_device(t.data_ptr(), n, y.data_ptr(), cap, stream)
+            return y[:got]
+        raw = _integer_iq(x, scale)
+        if raw is not None:
+            return self._h.work_raw(raw[0], raw[1], scale)[0]
+        return self._h.work(np.asarray(x, dtype=np.complex64))[0]
+
+    def reset(self):
+        """Drops the carried items: the next item is sample 0 of a new stream."""
         self._h.reset()
 
     def kernel_ms(self) -> float:
