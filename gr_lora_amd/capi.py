@@ -26,7 +26,7 @@ EXPORTS = [
     "lora_hip_get_geometry", "lora_hip_set_sf", "lora_hip_set_samp_rate", "lora_hip_work", "lora_hip_flush",
     "lora_hip_decode_device", "lora_hip_frames_available", "lora_hip_poll_frame", "lora_hip_drain_frames", "lora_hip_drain_slots", "lora_hip_demod_symbols_device", "lora_hip_demod_symbols_ex_device",
     "lora_hip_last_timing", "lora_hip_last_plan", "lora_hip_get_table", "lora_hip_last_payload_pass", "lora_hip_gap_starts_device", "lora_hip_decode_device_begin", "lora_hip_decode_device_end", "lora_hip_decode_device_prepass", "lora_hip_trace", "lora_hip_trace_clear", "lora_hip_check_frame", "lora_hip_estimate_cfo_device", "lora_hip_ref_ifreq_device",
-    "lora_hip_set_stream_latency", "lora_hip_stream_info", "lora_hip_walker_kernel_name", "lora_hip_window_stats_device", "lora_hip_detect_preambles_device", "lora_hip_decode_at_headers_device",
+    "lora_hip_set_stream_latency", "lora_hip_stream_info", "lora_hip_stream_info_ex", "lora_hip_walker_kernel_name", "lora_hip_window_stats_device", "lora_hip_detect_preambles_device", "lora_hip_decode_at_headers_device",
     "lora_hip_mux_create", "lora_hip_mux_destroy", "lora_hip_mux_work", "lora_hip_mux_flush", "lora_hip_mux_set_latency", "lora_hip_mux_set_max_ahead", "lora_hip_mux_frames_available",
     "lora_hip_mux_poll_frame", "lora_hip_mux_passes", "lora_hip_mux_last_error",
     "lora_hip_iq_item_bytes", "lora_hip_iq_unpack_device", "lora_hip_work_raw",
@@ -142,7 +142,8 @@ class FrameCheck(C.Structure):
 
 class StreamInfo(C.Structure):
     _fields_ = [("batch_items", C.c_uint64), ("buffered_items", C.c_uint64), ("passes", C.c_uint64), ("passes_by_latency", C.c_uint64),
-                ("consumed_base", C.c_int64), ("max_latency_ms", C.c_float), ("pass_in_flight", C.c_uint32)]
+                ("consumed_base", C.c_int64), ("max_latency_ms", C.c_float), ("pass_in_flight", C.c_uint32),
+                ("resume_pos", C.c_int64), ("resume_cr", C.c_uint32), ("reserved", C.c_uint32)]   # (lora_hip_stream_info_ex)
 
 
 class WindowStats(C.Structure):
@@ -296,6 +297,8 @@ def load():
     L.lora_hip_mux_last_error.restype = C.c_char_p
     L.lora_hip_set_stream_latency.argtypes = [vp, C.c_float]
     L.lora_hip_stream_info.argtypes = [vp, C.POINTER(StreamInfo)]
+    if hasattr(L, "lora_hip_stream_info_ex") or not os.environ.get("LORA_HIP_LIB"):   # (a library variant of an older ABI under tools/ab.sh does without)
+        L.lora_hip_stream_info_ex.argtypes = [vp, C.POINTER(StreamInfo), C.c_uint32]
     L.lora_hip_check_frame.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(FrameCheck)]
     L.lora_hip_check_frame.restype = C.c_int
     L.lora_hip_channelizer_create.argtypes = [C.POINTER(ChannelizerConfig), C.POINTER(vp)]
@@ -504,8 +507,12 @@ class Handle:
         self._check(self.L.lora_hip_set_stream_latency(self.h, float(max_latency_ms)))
 
     def stream_info(self) -> StreamInfo:
+        """lora_hip_stream_info_ex: with resume_pos / resume_cr, the serial decoder's state behind the last collected pass."""
         out = StreamInfo()
-        self._check(self.L.lora_hip_stream_info(self.h, C.byref(out)))
+        if hasattr(self.L, "lora_hip_stream_info_ex"):
+            self._check(self.L.lora_hip_stream_info_ex(self.h, C.byref(out), C.sizeof(StreamInfo)))
+        else:
+            self._check(self.L.lora_hip_stream_info(self.h, C.byref(out)))
         return out
 
     # batched, device-resident

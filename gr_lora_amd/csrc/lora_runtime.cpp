@@ -103,11 +103,8 @@ struct DevBuf {
 
 // The streaming pipeline under lora_hip_work (one channel) and lora_hip_mux (n channels): see the description above pipe_init().
 struct ChunkPipe {
-    struct Chan {
-        size_t fill = 0, tail_len = 0; // items of the chunk being filled uploaded (or queued for upload) so far; items carried over in front of it
-        uint32_t cr = 0;               // decoder state carried from pass to pass: d_phdr.cr, power queue,
-        PwrState pwr;
-        int64_t host_base = 0;         // ... and the absolute item index of the first item of the channel's next stream region
+    struct Chan : StreamCarry {        // (lora_stitch.hpp: what a channel carries from pass to pass, and the rule it is carried by)
+        size_t fill = 0;               // items of the chunk being filled uploaded (or queued for upload) so far
     };
     std::vector<Chan> ch;
     DevBuf<float2> dbuf[2];            // per channel a region [ tail area (tailcap items, right-aligned) | chunk (batch items) ]
@@ -160,6 +157,8 @@ struct lora_hip_decoder {
     // a pass between lora_hip_decode_device_begin and _end
     PassCtx pass;
     std::vector<StreamDesc> pass_streams;
+    int64_t resume_pos = 0;            // stream 0 behind the last collected pass (lora_hip_stream_info_ex): the serial decoder's position
+    uint32_t resume_cr = 0;            // ... and d_phdr.cr
     const float2 *pass_iq = nullptr;
     hipStream_t pass_st = nullptr;
     bool pass_open = false, iq_ready = false;
@@ -1169,10 +1168,9 @@ lora_hip_status pipe_collect(lora_hip_decoder *h)
     bool any_tail = false;
     for (const StreamDesc &sd : h->pass_streams) {
         ChunkPipe::Chan &c = p.ch[sd.id];
-        c.cr = sd.cr_out; c.pwr = sd.pwr;
-        const size_t keep_from = (size_t)std::min<int64_t>(std::max<int64_t>(sd.final_pos, 0), (int64_t)sd.len);
-        const size_t tail = sd.len - keep_from; // an attempt that ran out of data is re-run from its start with the next chunk behind it
-        c.host_base += (int64_t)keep_from;
+        const size_t keep_from = carry_collect(c, sd);
+        if (sd.id == 0u) { h->resume_pos = c.host_base; h->resume_cr = c.cr; }
+        const size_t tail = c.tail_len; // an attempt that ran out of data is re-run from the start of its scan with the next chunk behind it
         if (tail > p.tailcap) { // a packet longer than the tail area: grow both buffers, every region keeps its chunk and the right end of its tail area
             const size_t ncap = std::max(2u * p.tailcap, tail + (size_t)h->P.sps), nregion = ncap + p.batch;
             HIP_TRY(h, hipStreamSynchronize(p.copy_st));
@@ -1194,7 +1192,6 @@ lora_hip_status pipe_collect(lora_hip_decoder *h)
                                       hipMemcpyDeviceToDevice, p.comp_st));
             any_tail = true;
         }
-        c.tail_len = tail;
     }
     if (any_tail) { // the sources sit in chunk areas the next uploads overwrite: they wait for these copies
         HIP_TRY(h, hipEventRecord(p.tail_ev, p.comp_st));
@@ -1225,11 +1222,9 @@ lora_hip_status pipe_rotate(lora_hip_decoder *h, bool by_latency)
     sds.clear();
     for (uint32_t c = 0; c < p.ch.size(); c++) {
         ChunkPipe::Chan &C = p.ch[c];
-        const size_t len = C.tail_len + C.fill;
-        if (len < 2u * (size_t)h->P.sps) continue;
         StreamDesc sd{};
-        sd.off = (uint64_t)c * p.region + p.tailcap - C.tail_len; sd.len = len; sd.id = c;
-        sd.cr_in = C.cr; sd.pwr = C.pwr; sd.abs_base = C.host_base;
+        if (!carry_launch(C, C.fill, h->P.sps, sd)) continue;
+        sd.off = (uint64_t)c * p.region + p.tailcap - C.tail_len; sd.id = c;
         sds.push_back(sd);
     }
     if (sds.empty()) return LORA_HIP_OK;
@@ -1443,7 +1438,9 @@ lora_hip_status lora_hip_decode_device_end(lora_hip_decoder_t *h)
     // d_phdr.cr and power queue behind - that pass belongs to lora_hip_work / lora_hip_flush)
     if (h->pipe.inflight) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_decode_device_end: the open pass is lora_hip_work's; call lora_hip_flush");
     HIP_TRY(h, hipSetDevice(h->device));
-    return pass_end(h);
+    const lora_hip_status s = pass_end(h);
+    if (s == LORA_HIP_OK && !h->pass_streams.empty()) { h->resume_pos = h->pass_streams[0].final_pos; h->resume_cr = h->pass_streams[0].cr_out; }
+    return s;
 }
 
 lora_hip_status lora_hip_decode_device(lora_hip_decoder_t *h, const void *d_iq, size_t total_items,
@@ -1598,6 +1595,17 @@ lora_hip_status lora_hip_set_stream_latency(lora_hip_decoder_t *h, float max_lat
 {
     if (!h || !(max_latency_ms >= 0.0f)) return LORA_HIP_ERR_ARG;
     h->pipe.max_latency_ms = max_latency_ms;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_stream_info_ex(const lora_hip_decoder_t *h, lora_hip_stream_info_t *out, uint32_t struct_size)
+{
+    if (!h || !out || struct_size < offsetof(lora_hip_stream_info_t, resume_pos)) return LORA_HIP_ERR_ARG;
+    lora_hip_stream_info_t full{};
+    const lora_hip_status s = lora_hip_stream_info(h, &full);
+    if (s != LORA_HIP_OK) return s;
+    full.resume_pos = h->resume_pos; full.resume_cr = h->resume_cr;
+    std::memcpy(out, &full, std::min<size_t>(struct_size, sizeof full));
     return LORA_HIP_OK;
 }
 

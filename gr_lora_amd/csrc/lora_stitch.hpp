@@ -59,11 +59,47 @@ struct StreamDesc {
     uint32_t cr_in;       // d_phdr.cr carried in
     PwrState pwr;         // power queue / snr carried in
     int64_t  abs_base;    // added to reported positions
-    // results
+    // results: the serial decoder's state at the end of the pass.  incomplete: the data ended inside an attempt - final_pos is then the start
+    // of that attempt's DETECT scan (the end of the attempt before it, or the start of the pass), cr_out the d_phdr.cr the decoder held THERE (the
+    // pending attempt's cr_prev, not the CR of the header it may have decoded since) and pwr the power state there: the next pass runs the
+    // attempt again from that state
     int64_t  final_pos = 0;
     uint32_t cr_out = 0;
     bool incomplete = false;
+    // while a pass is stitched: where the DETECT scan the true trajectory is in began, and the power state there
+    int64_t  scan_pos = 0;
+    PwrState scan_pwr;
 };
+
+// What a stream carries from one pass to the next (lora_hip_work, the mux, the gateways; tests/host_sim runs the same two functions): d_phdr.cr,
+// the power state, the absolute index of its next item and the items kept in front of the next chunk.
+struct StreamCarry {
+    size_t   tail_len = 0;  // items carried over in front of the chunk being filled
+    uint32_t cr = 0;        // decoder state carried from pass to pass: d_phdr.cr, power queue,
+    PwrState pwr;
+    int64_t  host_base = 0; // ... and the absolute item index of the first item of the stream's next region
+};
+
+// The end of a pass: takes the decoder state; returns the item of the pass's region from which on the stream is kept (an attempt that ran out
+// of data is run again from the start of its scan with the next chunk behind it)
+inline size_t carry_collect(StreamCarry &c, const StreamDesc &sd)
+{
+    c.cr = sd.cr_out; c.pwr = sd.pwr;
+    const size_t keep_from = (size_t)std::min<int64_t>(std::max<int64_t>(sd.final_pos, 0), (int64_t)sd.len);
+    c.host_base += (int64_t)keep_from;
+    c.tail_len = (size_t)sd.len - keep_from;
+    return keep_from;
+}
+
+// The start of the next: the carried items and `fill` new ones as one stream (off and id are the caller's).  False: fewer than two symbols
+// (the reference's set_output_multiple(2 * sps), decoder_impl.cc:91: work() runs only while that many items remain), the stream stays out of the pass and goes on filling.
+inline bool carry_launch(const StreamCarry &c, size_t fill, uint32_t sps, StreamDesc &sd)
+{
+    const size_t len = c.tail_len + fill;
+    if (len < 2u * (size_t)sps) return false;
+    sd.len = len; sd.cr_in = c.cr; sd.pwr = c.pwr; sd.abs_base = c.host_base;
+    return true;
+}
 
 // Attempt records of one launch: storage that is neither cleared nor reallocated between launches (a 58-deep
 // std::vector<AttemptRec> per job would be megabytes to zero-fill and to page in on every call).
@@ -131,9 +167,29 @@ void adopt(Env &env, const AttemptRec &r, StreamDesc &sd)
     sd.pwr.apply(r.npush, r.push_tail);
     sd.pwr.determine_snr();
     if (r.status == kAttemptFrame) env.publish(r, sd);
+    sd.scan_pos = r.end_pos; sd.scan_pwr = sd.pwr; // the next DETECT scan begins here
 }
 
 struct Cursor { int64_t pos; uint32_t cr; }; // DETECT state between attempts: position + carried d_phdr.cr
+
+// The record of the attempt run `job` was cut short in (JobResult.pad), or null: none pending, or its record did not fit the record capacity
+// (the kernels begin no attempt without room for its record; a caller that meets it all the same adopts nothing of the run)
+inline const AttemptRec *pending_rec(const RunOut &R, size_t job)
+{
+    const JobResult &jr = R.res[job];
+    return (jr.pad && jr.n_attempts >= 1u && jr.n_attempts - 1u < R.cap) ? &R.rec(job, jr.n_attempts - 1u) : nullptr;
+}
+inline bool end_known(const RunOut &R, size_t job) { return !R.res[job].pad || pending_rec(R, job) != nullptr; }
+
+// The DETECT state run `job` ended in.  With an attempt pending that is the start of the attempt and the d_phdr.cr it STARTED with (its record's
+// cr_prev): JobResult.final_cr is the kernels' d_phdr.cr where they stopped, behind the pending attempt's header if it got that far, which the serial
+// decoder does not hold at final_pos - resuming a stream with it decodes the packet's header on the branch of its own CR (:655).  (end_known first.)
+inline Cursor end_cursor(const RunOut &R, size_t job)
+{
+    const JobResult &jr = R.res[job];
+    const AttemptRec *p = pending_rec(R, job);
+    return Cursor{jr.final_pos, p ? p->cr_prev : jr.final_cr};
+}
 
 // A job that walks stream sd from the state `from` up to `limit`; stop_at_header: a probe, which stops on entering the first header
 inline Job walk_job(const StreamDesc &sd, Cursor from, int64_t limit, bool stop_at_header)
@@ -182,10 +238,14 @@ int run_serial(Env &env, StreamDesc &sd, Cursor &cur, int64_t limit, bool tracin
         if (s != 0) return s;
         const JobResult &jr = out.res[0];
         if (debug_jobs_on()) dump_job("serial", 0, jobs[0], out);
+        if (!end_known(out, 0)) { // (a pending attempt without its record: not a state to go on from, and the kernels never report one)
+            if (debug_on()) fprintf(stderr, "[lora_hip] serial walk of stream %u from %lld: %u attempts, the pending one's record did not fit %u records - the decode fails\n",
+                                    sd.id, (long long)cur.pos, jr.n_attempts, out.cap);
+            return -1;
+        }
         for (uint32_t a = 0; a < out.n_done(0); a++) adopt(env, out.rec(0, a), sd);
         if (tracing) env.append_trace(out, 0, trace_cap, sd.abs_base);
-        cur.cr = jr.final_cr;
-        cur.pos = jr.final_pos; // start of the pending attempt when one was cut short
+        cur = end_cursor(out, 0); // start and carried-in CR of the pending attempt when one was cut short
         if (jr.pad) { sd.incomplete = true; return 0; }
         sd.pwr.apply(jr.npush, jr.push_tail);
         if (jr.stop_reason != 2u) return 0;
@@ -885,9 +945,10 @@ bool adopt_from_header(Env &env, StreamDesc &sd, Cursor &cur, const AttemptRec &
     sd.pwr.apply(L.npush, L.push_tail);
     sd.pwr.determine_snr();
     if (publish_any || R.rec(job, a).status == kAttemptFrame) env.publish(R.rec(job, a), sd);
+    sd.scan_pos = R.rec(job, a).end_pos; sd.scan_pwr = sd.pwr;
     for (uint32_t b = a + 1u; b < R.n_done(job); b++) adopt(env, R.rec(job, b), sd);
     const JobResult &jr = R.res[job];
-    cur = Cursor{jr.final_pos, jr.final_cr};
+    cur = end_cursor(R, job);
     if (jr.pad) { sd.incomplete = true; return false; }
     sd.pwr.apply(jr.npush, jr.push_tail);
     return true;
@@ -900,13 +961,15 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
     const uint32_t sps = env.sps();
     const std::vector<Seg> &segs = ctx.segs;
     const size_t f = ctx.first_seg[i];
+    sd.scan_pos = segs[f].b0; sd.scan_pwr = sd.pwr;
     // the first segment starts from the true state: adopt it wholesale
-    for (uint32_t a = 0; a < R1.n_done(f); a++) adopt(env, R1.rec(f, a), sd);
+    const bool first_known = end_known(R1, f);
+    for (uint32_t a = 0; first_known && a < R1.n_done(f); a++) adopt(env, R1.rec(f, a), sd);
     if (ctx.tracing) env.append_trace(R1, (uint32_t)f, ctx.trace_cap, sd.abs_base);
-    Cursor cur{R1.res[f].final_pos, R1.res[f].final_cr};
-    int64_t covered = segs[f].b1; // the true trajectory is known up to here
-    if (R1.res[f].pad) sd.incomplete = true;
-    else sd.pwr.apply(R1.res[f].npush, R1.res[f].push_tail);
+    Cursor cur = first_known ? end_cursor(R1, f) : Cursor{segs[f].b0, sd.cr_in};
+    int64_t covered = first_known ? segs[f].b1 : segs[f].b0; // the true trajectory is known up to here
+    if (first_known && R1.res[f].pad) sd.incomplete = true;
+    else if (first_known) sd.pwr.apply(R1.res[f].npush, R1.res[f].push_tail);
     auto serial_to = [&](int64_t limit, const char *why) -> int {
         if (debug_on()) fprintf(stderr, "[lora_hip] serial fallback stream %u pos %lld -> %lld: %s\n", sd.id, (long long)cur.pos, (long long)limit, why);
         env.count_slow_path();
@@ -914,7 +977,9 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
         covered = std::max(covered, limit);
         return r;
     };
-    if (!sd.incomplete && R1.res[f].stop_reason == 2u)
+    if (!first_known) {
+        if (const int r = serial_to(segs[f].b1, "first segment's pending record did not fit")) return r;
+    } else if (!sd.incomplete && R1.res[f].stop_reason == 2u)
         if (const int r = serial_to(segs[f].b1, "first segment out of records")) return r;
     for (size_t q = plan.first_probe[i]; q < plan.first_probe[i + 1] && !sd.incomplete; q++) {
         const Probe &pb = plan.probes[q];
@@ -926,7 +991,11 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
         }
         const ProbeView &view = pv[q];
         const JobResult &pr = view.res;
-        // lost-sync attempts the true trajectory went through before the header
+        if (pr.pad && pr.n_attempts > view.cap) { // the pending attempt's record did not fit: nothing of the probe is adopted, the cursor stands
+            if (const int r = serial_to(b1, "probe out of records")) return r;
+            continue;
+        }
+        // the attempts the true trajectory completed before the header: lost-sync ones, and a whole-segment probe's frames
         for (uint32_t a = 0; a < view.n_done(); a++) adopt(env, view.recs[a], sd);
         if (!pr.pad) { // no header before the probe's limit
             cur = Cursor{pr.final_pos, pr.final_cr};
@@ -936,13 +1005,9 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
                 if (const int r = serial_to(b1, "probe ended without a header")) return r;
             continue;
         }
-        if (pr.n_attempts > view.cap) { // the pending attempt's record did not fit
-            if (const int r = serial_to(b1, "probe out of records")) return r;
-            continue;
-        }
         const AttemptRec &L = view.recs[pr.n_attempts - 1u];
-        if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header
-            cur.pos = L.start_pos;
+        if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header (a whole-segment probe: or inside a packet)
+            cur = Cursor{L.start_pos, L.cr_prev};
             sd.incomplete = true;
             break;
         }
@@ -960,11 +1025,12 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
                 return header_bearing(r, false) && (at_sfd ? passed_sfd_state(r, probe_sfd_pos, probe_sfd_fails) : r.hdr_pos == L.hdr_pos) &&
                        !wrong_fec_branch(r, L.cr_prev);
             });
+            if (match >= 0 && !end_known(R1, k)) match = -1;
         }
         if (match < 0 && pb.rep_out && !at_sfd) { // the rest of the target segment, run again from the true header
             const RunOut &RR = *pb.rep_out;
             const size_t rj = pb.rep_job;
-            if (RR.n_done(rj) >= 1u && RR.rec(rj, 0).hdr_pos == L.hdr_pos && RR.res[rj].stop_reason != 2u) {
+            if (RR.n_done(rj) >= 1u && RR.rec(rj, 0).hdr_pos == L.hdr_pos && RR.res[rj].stop_reason != 2u && end_known(RR, rj)) {
                 if (!adopt_from_header(env, sd, cur, L, RR, rj, 0, false)) break;
                 covered = std::max(covered, b1);
                 env.count_repair();
@@ -1000,6 +1066,10 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
     // whatever the probes did not cover is walked serially (exactness before speed)
     if (!sd.incomplete && cur.pos < (int64_t)sd.len && covered < (int64_t)sd.len && cur.pos + 2 * (int64_t)sps <= (int64_t)sd.len)
         if (const int r = serial_to((int64_t)sd.len, "uncovered tail")) return r;
+    if (sd.incomplete) { // the attempt is run again from the start of its scan, wherever a job or probe of this pass took the scan up
+        cur.pos = sd.scan_pos;
+        sd.pwr = sd.scan_pwr;
+    }
     sd.final_pos = cur.pos;
     sd.cr_out = cur.cr;
     return 0;

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define LORA_HIP_ABI_VERSION 4   /* 4: lora_hip_get_table; 3: LORA_HIP_FLAG_FAST_SYNC (strict SYNC is the default), lora_hip_ref_ifreq_device; 2: lora_hip_set_stream_latency, lora_hip_stream_info, lora_hip_walker_kernel_name, lora_hip_window_stats_device, lora_hip_detect_preambles_device, lora_hip_decode_at_headers_device, lora_hip_mux_* */
+#define LORA_HIP_ABI_VERSION 4   /* (still 4: lora_hip_stream_info_ex is an addition) 4: lora_hip_get_table; 3: LORA_HIP_FLAG_FAST_SYNC (strict SYNC is the default), lora_hip_ref_ifreq_device; 2: lora_hip_set_stream_latency, lora_hip_stream_info, lora_hip_walker_kernel_name, lora_hip_window_stats_device, lora_hip_detect_preambles_device, lora_hip_decode_at_headers_device, lora_hip_mux_* */
 
 typedef enum lora_hip_status {
     LORA_HIP_OK = 0,
@@ -193,8 +193,21 @@ typedef struct lora_hip_stream_info {
     int64_t  consumed_base;          /* absolute item index up to which the stream is decoded (frames before it are published) */
     float    max_latency_ms;
     uint32_t pass_in_flight;
+    /* (the two fields below: lora_hip_stream_info_ex only - lora_hip_stream_info writes the struct up to here, as before they existed) */
+    int64_t  resume_pos;             /* where the serial decoder stands behind the last collected pass, and ...                */
+    uint32_t resume_cr;              /* ... the d_phdr.cr it holds there: see lora_hip_stream_info_ex                           */
+    uint32_t reserved;
 } lora_hip_stream_info_t;
 lora_hip_status lora_hip_stream_info(const lora_hip_decoder_t *h, lora_hip_stream_info_t *out);
+/* As lora_hip_stream_info, with the resume state of stream 0 behind the last pass collected on this handle.  After
+ * lora_hip_decode_device(_end): resume_pos is relative to the stream's first item; after lora_hip_work / lora_hip_flush it is absolute
+ * (= consumed_base).  Where the data ended inside a packet it is the start of that packet's DETECT scan, and resume_cr the
+ * d_phdr.cr the decoder held THERE (:655: the packet's header is decoded on that branch, not on the branch of its own CR): a decoder
+ * constructed with cr = resume_cr and given the items from resume_pos on publishes what the serial decoder publishes from there
+ * (but for the SNR byte of its first frame where fewer than four DETECT steps precede it: the power queue is not part of this).
+ * struct_size: sizeof(lora_hip_stream_info_t) of the caller; no more than that is written.  LORA_HIP_ERR_ARG: h / out NULL, or
+ * struct_size smaller than the struct up to pass_in_flight.                                                                      */
+lora_hip_status lora_hip_stream_info_ex(const lora_hip_decoder_t *h, lora_hip_stream_info_t *out, uint32_t struct_size);
 
 /* ---- streaming, many channels through ONE decoder: the gateway flowgraph ---------------------------------------------
  * The reference decodes one channel per block (README.md:13, channelizer_impl.cc:47): a 64-channel gateway is 64 decoder
