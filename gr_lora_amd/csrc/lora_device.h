@@ -102,6 +102,8 @@ struct Job {
     uint32_t tail_stop_sfd; // 1: the tail probe (probe_limit) stops behind its FIRST FIND_SFD step instead of at the header (kAttemptAtSfd): two
                            // trajectories that start a FIND_SFD step at the same sample with the same d_corr_fails are one from there on
                            // (:785-818 read nothing else), and the successor's attempt records hold every such state it went through
+    uint32_t sync_succ;    // 1 + the index, in this launch, of the job of the next segment of the same stream (0: none).  With LaunchCfg.sync_pos the tail probe
+                           // ends where its first attempt leaves SYNC if that job's first attempt left SYNC at the same sample (kStopAtSync; walker2 SF7 / SF8)
 };
 
 struct AttemptRec {
@@ -130,7 +132,7 @@ struct JobResult {
     uint32_t final_cr;     // d_phdr.cr after the last attempt
     uint32_t npush;        // pushes of the trailing DETECT scan (after the last attempt)
     float    push_tail[4];
-    uint32_t stop_reason;  // 0 scan_limit reached, 1 out of data, 2 attempt capacity, 3 max_attempts / probe stop
+    uint32_t stop_reason;  // 0 scan_limit reached, 1 out of data, 2 attempt capacity, 3 max_attempts / probe stop; a tail probe's also kStopAtSync
     uint32_t n_steps;      // trace entries written
     uint32_t pad;
     uint32_t cyc[6];       // shader clocks / 64 spent per state (DETECT, SYNC, FIND_SFD, PAUSE, HEADER, PAYLOAD); walker2 only
@@ -142,6 +144,11 @@ struct JobResult {
     uint32_t ctl[4];       // control wavefront inside decode rounds, shader clocks / 64: state copy-in, symbol loop, plan, copy-out
     uint32_t dbg[6];       // diagnostics (walker2): HW_ID, XCC_ID, s_memrealtime (100 MHz) at the start and the end of the job, clock64 / 64 likewise
 };
+
+// tail_stop_reason of a tail probe that ended at its first SYNC exit: its successor's first attempt left SYNC at the same sample, and from there on
+// (position, FIND_SFD, d_corr_fails = 0, d_fine_sync = 0: all that :785-818 read) the two trajectories are one.  The pending record is the one the
+// out-of-data path writes (kAttemptOutOfData, hdr_pos = -1, end_pos = the FIND_SFD entry position).
+constexpr uint32_t kStopAtSync = 4;
 
 struct StepRec {           // mirrors lora_hip_step_t
     int32_t  state, consumed;
@@ -167,6 +174,9 @@ struct LaunchCfg {
     uint32_t *balance;       // kBalanceWords words, zero-initialised once (walker2: progress exchange between the workgroups of a CU), or nullptr
     uint32_t skip_payload;   // 1: the launch runs the kernels' header-only variant (walker3): a packet's attempt ends behind its header (kAttemptHeaderOnly) and the
                              // job goes on in DETECT where the payload would end if no symbol moved the clock; the payload pass (launch_payload_pass) does the rest
+    unsigned long long *sync_pos;   // n_jobs words, all zero when the launch begins, or nullptr (walker2 SF7 / SF8, the main launch of a pass): job k stores 1 + the position
+                                    // at which its FIRST attempt leaves SYNC for FIND_SFD; a tail probe compares its own with its successor's (Job.sync_succ)
+    unsigned long long *sync_clear; // n_jobs words of the array the NEXT such launch publishes in: job k zeroes word k (the two arrays take turns, so no launch waits for a fill)
 };
 constexpr uint32_t kBalanceCus = 2048;                 // (XCC_ID, SE, SH, CU) flattened
 constexpr uint32_t kBalanceWords = 3u * kBalanceCus;   // per CU: remaining work of its two workgroups, claim counter
@@ -212,6 +222,7 @@ struct PayloadOut {          // (device-written)
     uint8_t  frame[kMaxFrame + 4];
 };
 int launch_payload_chain(const DevParams &p, const uint32_t *d_bins, const int32_t *d_fine, const DemodAlt &alt, const PayloadDesc *descs, PayloadOut *outs, uint32_t n_packets, void *stream);
+bool walker_has_sync_stop(const DevParams &p);                              // LaunchCfg.sync_pos is honoured (walker2 at decimation 8, SF7 / SF8)
 bool walker_has_skip_variant(const DevParams &p);                           // LaunchCfg.skip_payload is honoured (walker3, explicit header)
 int launch_ref_ifreq(const float2 *x, uint32_t n, float *d_arg, float *d_ifreq, void *stream); // diagnostics: the strict SYNC path's atan2f / ifreq
 int launch_cfo(const DevParams &p, const float2 *iq, const int64_t *d_offsets, uint32_t n, int mode, float *d_out, void *stream); // N4: explicit CFO estimate

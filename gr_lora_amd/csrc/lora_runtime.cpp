@@ -152,7 +152,7 @@ struct lora_hip_decoder {
     hipEvent_t ev_pre0 = nullptr, ev_pre1 = nullptr, ev_dep = nullptr; // envelope pre-pass timing; dependency of the pre-pass stream on the caller's
     hipStream_t pre_stream = nullptr;  // the envelope pre-pass runs here, beside whatever the caller's stream is busy with
     // the main launch of a pass between run_jobs_begin and run_jobs_end
-    struct Pending { uint32_t nj = 0, recs_per_job = 0, eager = 0, trace_cap = 0; bool direct = true, open = false; hipStream_t st = nullptr;
+    struct Pending { uint32_t nj = 0, recs_per_job = 0, eager = 0, trace_cap = 0; bool direct = true, open = false, main = false; hipStream_t st = nullptr;
                      std::chrono::steady_clock::time_point hp0, hp1; } pending;
     // a pass between lora_hip_decode_device_begin and _end
     PassCtx pass;
@@ -175,6 +175,14 @@ struct lora_hip_decoder {
     PinnedBuf<AttemptRec> p_recs;
     // burst-envelope pre-pass (segment planning)
     DevBuf<uint32_t> d_balance;             // LaunchCfg::balance, zeroed when allocated
+    // LaunchCfg::sync_pos / sync_clear: two arrays that take turns.  The launch that publishes in one zeroes the other, word k by job k, so the next launch finds
+    // its array clean without a fill on the stream; sync_dirty[i] = leading words of array i that may be non-zero (a fill is queued only when a launch's jobs did
+    // not cover them: the job count of a pass grew)
+    DevBuf<unsigned long long> d_sync[2];
+    uint32_t sync_dirty[2] = {0, 0};
+    int sync_cur = 0;
+    bool sync_next = false;                 // the next run_jobs_begin is the main launch of a pass (DeviceEnv::run_jobs_begin): its tail probes may end at SYNC
+    uint32_t last_tail_probes = 0, last_sync_stops = 0; // the last main launch: tail probes that reached a packet, those of them that ended at SYNC
     DevBuf<float> d_env_E;
     DevBuf<unsigned long long> d_env_buf;   // gap-start bitmap, one bit per block
     PinnedBuf<EnvStream> p_env_streams;
@@ -488,6 +496,31 @@ lora_hip_status run_jobs_begin(lora_hip_decoder *h, const float2 *d_iq, const st
     }
     c.balance = no_balance ? nullptr : h->d_balance.p;
     c.skip_payload = h->launch_skip ? 1u : 0u;
+    // the main launch of a pass: its tail probes end at SYNC where their successor left SYNC at the same sample (Job.sync_succ indexes THIS launch's jobs: re-runs,
+    // probes and repairs get no array).  LORA_HIP_NO_SYNC_STOP=1: every tail probe runs on to its header (A/B, tests)
+    static const bool no_sync_stop = getenv("LORA_HIP_NO_SYNC_STOP") != nullptr;
+    const bool main_launch = h->sync_next;
+    h->sync_next = false;
+    h->pending.main = main_launch;
+    bool sync_stop = main_launch && !no_sync_stop && !trace_cap && !h->launch_skip && walker_has_sync_stop(h->P);
+    if (sync_stop) {
+        sync_stop = false;
+        for (const Job &j : jobs) sync_stop = sync_stop || j.sync_succ != 0u;
+    }
+    if (sync_stop) {
+        const int a = h->sync_cur, b = a ^ 1;
+        for (int i = 0; i < 2; i++) {
+            if (h->d_sync[i].cap >= nj) continue;
+            HIP_TRY(h, h->d_sync[i].reserve(nj));
+            HIP_TRY(h, hipMemsetAsync(h->d_sync[i].p, 0, h->d_sync[i].cap * sizeof(unsigned long long), st));
+            h->sync_dirty[i] = 0;
+        }
+        if (h->sync_dirty[a]) HIP_TRY(h, hipMemsetAsync(h->d_sync[a].p, 0, h->sync_dirty[a] * sizeof(unsigned long long), st)); // (the launch before this one had fewer jobs than the one before it)
+        c.sync_pos = h->d_sync[a].p; c.sync_clear = h->d_sync[b].p;
+        h->sync_dirty[a] = nj;
+        if (h->sync_dirty[b] <= nj) h->sync_dirty[b] = 0;
+        h->sync_cur = b;
+    }
     HIP_TRY(h, hipEventRecord(h->ev0, st));
     if (nj >= h->last_kernel_jobs) { h->last_kernel = walker_kernel_name_for(h->P, nj, h->launch_skip); h->last_kernel_jobs = nj; } // (the pass's main launch: probe and fix-up launches are smaller)
     if (launch_walker(h->P, c, st) != 0) return fail(h, LORA_HIP_ERR_HIP, "walker launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -521,14 +554,14 @@ lora_hip_status run_jobs_end(lora_hip_decoder *h, RunOut &out)
         fprintf(stderr, "[lora_hip] per-job avg kcycles (rounds): DETECT %.0f (%.1f) SYNC %.0f (%.1f) SFD %.0f (%.1f) PAUSE %.0f (%.1f) HDR %.0f (%.1f) PAYLOAD %.0f (%.1f)\n",
                 cyc[0] / nj / 1e3, rnd[0] / nj, cyc[1] / nj / 1e3, rnd[1] / nj, cyc[2] / nj / 1e3, rnd[2] / nj, cyc[3] / nj / 1e3, rnd[3] / nj, cyc[4] / nj / 1e3, rnd[4] / nj, cyc[5] / nj / 1e3, rnd[5] / nj);
         {
-            double na = 0, nt = 0, ntv = 0; uint32_t sr[4] = {0, 0, 0, 0}, tsr[4] = {0, 0, 0, 0}, tpad = 0;
+            double na = 0, nt = 0, ntv = 0; uint32_t sr[4] = {0, 0, 0, 0}, tsr[5] = {0, 0, 0, 0, 0}, tpad = 0;
             for (uint32_t j = 0; j < nj; j++) {
                 const JobResult &r = out.res[j];
                 na += r.n_attempts; sr[r.stop_reason & 3u]++;
-                if (r.tail_valid) { ntv++; nt += r.tail_n_attempts; tsr[r.tail_stop_reason & 3u]++; tpad += r.tail_pad; }
+                if (r.tail_valid) { ntv++; nt += r.tail_n_attempts; tsr[r.tail_stop_reason == kStopAtSync ? 4u : r.tail_stop_reason & 3u]++; tpad += r.tail_pad; }
             }
-            fprintf(stderr, "[lora_hip] attempts/job %.2f, stop reasons %u/%u/%u/%u; tails %.0f (attempts/tail %.2f, stop reasons %u/%u/%u/%u, pending %u)\n", na / nj, sr[0], sr[1],
-                    sr[2], sr[3], ntv, ntv ? nt / ntv : 0.0, tsr[0], tsr[1], tsr[2], tsr[3], tpad);
+            fprintf(stderr, "[lora_hip] attempts/job %.2f, stop reasons %u/%u/%u/%u; tails %.0f (attempts/tail %.2f, stop reasons %u/%u/%u/%u/%u, pending %u)\n", na / nj, sr[0], sr[1],
+                    sr[2], sr[3], ntv, ntv ? nt / ntv : 0.0, tsr[0], tsr[1], tsr[2], tsr[3], tsr[4], tpad);
         }
         double ctl[4] = {0};
         for (uint32_t j = 0; j < nj; j++) for (int i = 0; i < 4; i++) ctl[i] += 64.0 * out.res[j].ctl[i];
@@ -569,9 +602,18 @@ lora_hip_status run_jobs_end(lora_hip_decoder *h, RunOut &out)
             std::memcpy(&out.recs[(size_t)j * stride + a], src, n);
         }
     }
-    if (dbg_stats && h->P.use_fast) { // acquisitions (SYNC steps) per published frame; tail probes that stopped behind their first FIND_SFD step
-        double sync_rounds = 0; uint32_t frames = 0, tails = 0, early = 0;
+    if (h->pending.main) { // (lora_hip_last_sync_stops: two words per job already in cache)
+        uint32_t tails = 0, at_sync = 0;
         for (uint32_t j = 0; j < nj; j++) {
+            const JobResult &r = out.res[j];
+            if (r.tail_valid && r.tail_pad) { tails++; at_sync += r.tail_stop_reason == kStopAtSync ? 1u : 0u; }
+        }
+        h->last_tail_probes = tails; h->last_sync_stops = at_sync;
+    }
+    if (dbg_stats && h->P.use_fast) { // acquisitions (SYNC steps) per published frame; tail probes that stopped behind their first FIND_SFD step, or at SYNC
+        double sync_rounds = 0; uint32_t frames = 0, tails = 0, early = 0, at_sync = 0;
+        for (uint32_t j = 0; j < nj; j++) {
+            at_sync += (out.res[j].tail_valid && out.res[j].tail_pad && out.res[j].tail_stop_reason == kStopAtSync) ? 1u : 0u;
             const JobResult &r = out.res[j];
             sync_rounds += r.rounds[1];
             const uint32_t used = std::min(std::min(eager, max_att), r.n_attempts + (r.tail_valid ? r.tail_n_attempts : 0u));
@@ -581,8 +623,8 @@ lora_hip_status run_jobs_end(lora_hip_decoder *h, RunOut &out)
                 if (r.tail_valid && a + 1u == r.n_attempts + r.tail_n_attempts && r.tail_pad) { tails++; early += t.status == kAttemptAtSfd ? 1u : 0u; }
             }
         }
-        fprintf(stderr, "[lora_hip] acquisitions: %.0f SYNC rounds for %u frames of this launch (%.2f per frame); %u tail probes reached a packet, %u of them stopped behind their first FIND_SFD step\n",
-                sync_rounds, frames, frames ? sync_rounds / frames : 0.0, tails, early);
+        fprintf(stderr, "[lora_hip] acquisitions: %.0f SYNC rounds for %u frames of this launch (%.2f per frame); %u tail probes reached a packet, %u of them stopped behind their first FIND_SFD step, %u at SYNC\n",
+                sync_rounds, frames, frames ? sync_rounds / frames : 0.0, tails, early, at_sync);
     }
     h->eager_recs = std::min(std::max(max_att, 2u), 8u);
     bool more = false;
@@ -939,6 +981,7 @@ struct DeviceEnv {
     }
     int run_jobs_begin(const std::vector<Job> &jobs, uint32_t rpj, uint32_t trace_cap, RunOut &out)
     {
+        h->sync_next = true; // (the main launch of a pass: the one whose jobs' sync_succ index each other)
         return ::run_jobs_begin(h, d_iq, jobs, rpj, trace_cap, st, out) == LORA_HIP_OK ? 0 : -1;
     }
     int run_jobs_end(RunOut &out) { return ::run_jobs_end(h, out) == LORA_HIP_OK ? 0 : -1; }
@@ -1332,6 +1375,7 @@ void lora_hip_destroy(lora_hip_decoder_t *h)
     for (int i = 0; i < 2; i++) { h->pipe.dbuf[i].release(); h->feed.stage[i].release(); }
     h->feed.d_raw.release();
     h->p_jobs.release(); h->p_res.release(); h->p_recs.release();
+    h->d_sync[0].release(); h->d_sync[1].release();
     h->d_balance.release(); h->d_env_E.release(); h->d_env_buf.release(); h->p_env_streams.release(); h->p_env_buf.release();
     for (hipEvent_t e : {h->ev0, h->ev1, h->ev_done, h->ev_pre0, h->ev_pre1, h->ev_dep, h->ev_pay0, h->ev_pay1, h->ev_pay_done, h->pipe.up_ev, h->pipe.tail_ev,
                          h->feed.stage_ev[0], h->feed.stage_ev[1]})
@@ -2191,6 +2235,15 @@ lora_hip_status lora_hip_last_plan(const lora_hip_decoder_t *h, uint32_t *burst_
     if (!h) return LORA_HIP_ERR_ARG;
     if (burst_aware) *burst_aware = h->last_plan_burst;
     if (segments) *segments = h->last_plan_segments;
+    return LORA_HIP_OK;
+}
+
+// (the main launch of the last pass: tail probes that reached a packet, and those of them that ended at SYNC on their successor's published position)
+lora_hip_status lora_hip_last_sync_stops(const lora_hip_decoder_t *h, uint32_t *tail_probes, uint32_t *at_sync)
+{
+    if (!h) return LORA_HIP_ERR_ARG;
+    if (tail_probes) *tail_probes = h->last_tail_probes;
+    if (at_sync) *at_sync = h->last_sync_stops;
     return LORA_HIP_OK;
 }
 

@@ -289,6 +289,24 @@ inline const AttemptRec *tail_probe_last(const RunOut &R, size_t k)
     return li < R.cap ? &R.rec(k, li) : nullptr;
 }
 
+// Did job k's tail probe end at its first SYNC exit (kStopAtSync)?  The device has then compared positions: the first attempt of job k + 1 of the same
+// launch left SYNC at the same sample, with d_corr_fails = 0 and d_fine_sync = 0 like the probe's - the FIND_SFD entry state, which is all that
+// decoder_impl.cc:785-818 read.  From there on that attempt IS the true trajectory: its FIND_SFD steps, its header entry (or its loss of sync), all
+// that follows.  What the two do not share lies outside the kernels' comparison and is checked here as for any probe: d_phdr.cr, which picks the
+// header's FEC branch (wrong_fec_branch; the probe's pending record carries the true one), and the power queue, which only DETECT steps push to
+// (:360) - every push of the true scan precedes the probe's SYNC exit and is in its record, FIND_SFD and PAUSE push nothing.
+inline bool tail_at_sync(const RunOut &R, size_t k)
+{
+    const JobResult &jr = R.res[k];
+    return jr.tail_valid && jr.tail_pad && jr.tail_stop_reason == kStopAtSync;
+}
+// ... and the record of the successor job `succ` such a probe is merged with: its first, if that went on into a header (0), else -1 (the attempt lost
+// sync: what follows it depends on nothing but the position, but its later headers are decoded under the job's own d_phdr.cr - left to a probe)
+inline int sync_stop_match(const RunOut &R, size_t succ, bool with_header_only)
+{
+    return (R.res[succ].n_attempts >= 1u && R.cap >= 1u && R.rpj >= 1u && header_bearing(R.rec(succ, 0), with_header_only)) ? 0 : -1;
+}
+
 // The first of job k's completed or pending records that satisfies pred, or -1
 template <class Pred>
 int find_record(const RunOut &R, size_t k, Pred pred)
@@ -518,6 +536,9 @@ int decode_begin(Env &env, std::vector<StreamDesc> &streams, PassCtx &ctx)
         // header-only job by a second acquisition - config 4 at 2 s per pass 49.4 -> 54.0 Gsamples/s, at 8 s the same either way)
         j.probe_limit = (segmenting && has_next && !no_tail && !ctx.decoupled) ? std::min<int64_t>((int64_t)sd.len, segs[k + 1].b1 + 16ll * sps) : 0;
         j.tail_stop_sfd = (j.probe_limit && env.early_probe()) ? 1u : 0u;
+        // the job whose first SYNC exit the tail probe may end on (kStopAtSync): the next segment's, job k + 1 of THIS launch - copies of the job that run in
+        // other launches (re-runs, repairs) drop it.  Kernels without the early stop, and launches without LaunchCfg.sync_pos, ignore it
+        j.sync_succ = (j.probe_limit && !j.tail_stop_sfd) ? (uint32_t)(k + 2u) : 0u;
         max_span = std::max<uint64_t>(max_span, (uint64_t)(segs[k].b1 - segs[k].b0));
     }
     ctx.rpj1 = recs_for(max_span, sps) + (segmenting ? ctx.rpj2 : 0u);
@@ -624,7 +645,7 @@ int payload_end(Env &env, const std::vector<StreamDesc> &streams, PassCtx &ctx, 
         if (plan[k].term < 0 || plan[k].term_kind != 2u) continue;
         const AttemptRec &r = R1.rec(k, (uint32_t)plan[k].term);
         Job j = ctx.jobs[k];
-        j.start = r.hdr_pos; j.start_at_header = 1; j.cr_prev = r.cr_prev;
+        j.start = r.hdr_pos; j.start_at_header = 1; j.cr_prev = r.cr_prev; j.sync_succ = 0;
         rjobs.push_back(j);
     }
     RunOut &R3 = env.run_out(1);
@@ -755,16 +776,17 @@ int rerun_wrong_branch(Env &env, const std::vector<StreamDesc> &streams, const P
     for (size_t i = 0; i < streams.size(); i++) {
         for (size_t k = ctx.first_seg[i] + 1; k < ctx.first_seg[i + 1]; k++) {
             const AttemptRec *L = tail_probe_last(R1, k - 1);
-            if (!L || (L->status != kAttemptAtHeader && L->status != kAttemptAtSfd)) continue;
-            const bool at_sfd = L->status == kAttemptAtSfd;
+            const bool at_sync = L && tail_at_sync(R1, k - 1);
+            if (!L || (!at_sync && L->status != kAttemptAtHeader && L->status != kAttemptAtSfd)) continue;
+            const bool at_sfd = !at_sync && L->status == kAttemptAtSfd;
             if (at_sfd && L->n_sfd == 0u) continue;
-            // the job's first header-bearing attempt on the probe's trajectory
-            const int a = find_record(R1, k, [&](const AttemptRec &r) {
+            // the job's first header-bearing attempt on the probe's trajectory (a probe that ended at SYNC: the job's first attempt)
+            const int a = at_sync ? sync_stop_match(R1, k, true) : find_record(R1, k, [&](const AttemptRec &r) {
                 return header_bearing(r, true) && (at_sfd ? passed_sfd_state(r, L->sfd_pos[L->n_sfd - 1u], L->sfd_fails[L->n_sfd - 1u]) : r.hdr_pos == L->hdr_pos);
             });
             if (a < 0 || !wrong_fec_branch(R1.rec(k, (uint32_t)a), L->cr_prev)) continue;
             Job j = ctx.jobs[k];
-            j.cr_prev = L->cr_prev;
+            j.cr_prev = L->cr_prev; j.sync_succ = 0;
             rjobs.push_back(j);
             rk.push_back(k);
         }
@@ -856,10 +878,17 @@ inline void plan_probes(uint32_t sps, const std::vector<StreamDesc> &streams, co
     for (Probe &pb : probes) {
         if (pb.job >= 0) continue;
         const AttemptRec *L = tail_probe_last(R1, (size_t)pb.tail_of);
-        if (!L || L->status != kAttemptAtSfd || L->n_sfd == 0u) continue;
-        const int64_t pos = L->sfd_pos[L->n_sfd - 1u];
-        const uint32_t fails = L->sfd_fails[L->n_sfd - 1u];
-        if (any_segment_record(R1, ctx.first_seg[pb.stream], pb.target, [&](const AttemptRec &r) { return passed_sfd_state(r, pos, fails); })) continue;
+        if (!L) continue;
+        if (tail_at_sync(R1, (size_t)pb.tail_of)) {
+            // (likewise a probe that ended at SYNC on the position of a successor whose first attempt then lost sync: the true trajectory loses sync
+            // there too, and the probe that would have walked on to the next header is run now)
+            if (pb.target == (size_t)pb.tail_of + 1u && sync_stop_match(R1, pb.target, true) >= 0) continue;
+        } else {
+            if (L->status != kAttemptAtSfd || L->n_sfd == 0u) continue;
+            const int64_t pos = L->sfd_pos[L->n_sfd - 1u];
+            const uint32_t fails = L->sfd_fails[L->n_sfd - 1u];
+            if (any_segment_record(R1, ctx.first_seg[pb.stream], pb.target, [&](const AttemptRec &r) { return passed_sfd_state(r, pos, fails); })) continue;
+        }
         Job j = walk_job(streams[pb.stream], pb.start, ctx.jobs[(size_t)pb.tail_of].probe_limit, true);
         if (repair) {
             // (round 6) ... and past it: the job walks the whole target segment from the true state - the true trajectory itself, adopted by the stitch as a probe that
@@ -1006,7 +1035,9 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
             continue;
         }
         const AttemptRec &L = view.recs[pr.n_attempts - 1u];
-        if (L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header (a whole-segment probe: or inside a packet)
+        // a tail probe that ended at its first SYNC exit, on the position the next segment's job published there (tail_at_sync); its record is an out-of-data one
+        const bool at_sync = pb.tail_of >= 0 && pr.stop_reason == kStopAtSync;
+        if (!at_sync && L.status != kAttemptAtHeader && L.status != kAttemptAtSfd) { // ran out of data before reaching a header (a whole-segment probe: or inside a packet)
             cur = Cursor{L.start_pos, L.cr_prev};
             sd.incomplete = true;
             break;
@@ -1018,7 +1049,12 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
         const uint32_t probe_sfd_fails = (at_sfd && L.n_sfd) ? L.sfd_fails[L.n_sfd - 1u] : 0u;
         int match = -1;
         size_t mk = 0;
-        for (size_t k = f + 1; k <= pb.target && match < 0; k++) {
+        if (at_sync) { // the same FIND_SFD entry state as the successor's first attempt: that record and all behind it, if its header stands under the true d_phdr.cr
+            mk = pb.target;
+            if (pb.target == (size_t)pb.tail_of + 1u && segs[mk].b1 > cur.pos) match = sync_stop_match(R1, mk, false);
+            if (match >= 0 && (wrong_fec_branch(R1.rec(mk, (uint32_t)match), L.cr_prev) || !end_known(R1, mk))) match = -1;
+        }
+        for (size_t k = f + 1; !at_sync && k <= pb.target && match < 0; k++) {
             if (segs[k].b1 <= cur.pos) continue;
             mk = k;
             match = find_record(R1, k, [&](const AttemptRec &r) { // (not a header-only record: a merge publishes the matched record's frame)
@@ -1027,7 +1063,7 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
             });
             if (match >= 0 && !end_known(R1, k)) match = -1;
         }
-        if (match < 0 && pb.rep_out && !at_sfd) { // the rest of the target segment, run again from the true header
+        if (match < 0 && pb.rep_out && !at_sfd && !at_sync) { // the rest of the target segment, run again from the true header
             const RunOut &RR = *pb.rep_out;
             const size_t rj = pb.rep_job;
             if (RR.n_done(rj) >= 1u && RR.rec(rj, 0).hdr_pos == L.hdr_pos && RR.res[rj].stop_reason != 2u && end_known(RR, rj)) {
@@ -1040,7 +1076,7 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
         if (match < 0) {
             if (debug_on()) {
                 fprintf(stderr, "[lora_hip] probe for segment %zu [%lld, %lld): start %lld cr %u -> trig %lld hdr %lld (stopped %s, FIND_SFD state %lld / %u)\n", pb.target, (long long)segs[pb.target].b0, (long long)b1,
-                        (long long)pb.start.pos, pb.start.cr, (long long)L.trig_pos, (long long)L.hdr_pos, at_sfd ? "behind its first FIND_SFD step" : "at the header", (long long)probe_sfd_pos, probe_sfd_fails);
+                        (long long)pb.start.pos, pb.start.cr, (long long)L.trig_pos, (long long)L.hdr_pos, at_sync ? "at SYNC" : at_sfd ? "behind its first FIND_SFD step" : "at the header", (long long)(at_sync ? L.end_pos : probe_sfd_pos), probe_sfd_fails);
                 for (size_t k = pb.target ? pb.target - 1 : 0; k <= pb.target; k++)
                     for (uint32_t a = 0; a < std::min(R1.res[k].n_attempts, R1.cap); a++) {
                         const AttemptRec &r = R1.rec(k, a);
@@ -1049,7 +1085,8 @@ int stitch_stream(Env &env, StreamDesc &sd, size_t i, const PassCtx &ctx, const 
                     }
             }
             cur = Cursor{L.start_pos, L.cr_prev};
-            if (const int r = serial_to(b1, at_sfd ? "no segment job passed through the probe's FIND_SFD state" : "no segment job entered the same header")) return r;
+            if (const int r = serial_to(b1, at_sync ? "the successor's first attempt, which left SYNC where the probe did, is not one to merge with"
+                                                     : at_sfd ? "no segment job passed through the probe's FIND_SFD state" : "no segment job entered the same header")) return r;
             continue;
         }
         if (R1.rec(mk, (uint32_t)match).status == kAttemptOutOfData) {

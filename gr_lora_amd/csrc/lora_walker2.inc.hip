@@ -82,7 +82,7 @@ struct alignas(16) W2Shared {
     W2State  st;
     W2Stats  stats;
     int64_t  ph_start;    // hand-over from the job proper to its tail probe (Job.probe_limit): start position,
-    uint32_t ph_go, ph_cr, ph_natt, ph_pad; // go flag, d_phdr.cr, attempt records used so far
+    uint32_t ph_go, ph_cr, ph_natt, ph_succ; // go flag, d_phdr.cr, attempt records used so far; Job.sync_succ (kept here from the job's start: the probe's SYNC exit reads it once)
     uint32_t det_streak;  // consecutive DETECT rounds planned so far (control thread): the first of a streak looks at fewer windows
     uint32_t prio;        // priority of the worker wavefronts for the coming rounds (see the balance exchange in the round loop)
     uint32_t words_pk[2]; // d_words of the current block, one byte per word (words < 256 for SF <= 8); control thread only
@@ -642,6 +642,17 @@ __device__ __forceinline__ void walker2_body(const DevParams &P, const LaunchCfg
     uint32_t *bal_mine = nullptr, *bal_other = nullptr;
     uint32_t bal_rem = 0xffffffffu, bal_seen = 0u, bal_slot = 0u; // control thread only
     if (t0) W.prio = 0u;
+    // Tail probes end at SYNC (LaunchCfg.sync_pos, the main launch of a pass): a job publishes where its FIRST attempt leaves SYNC, and the probe of the
+    // segment before it, leaving its own first SYNC at that very sample, has nothing more to show - (position, FIND_SFD, d_corr_fails = 0,
+    // d_fine_sync = 0) is all that :785-818 read, the two futures are one, and the host takes the successor's records from its first attempt on.
+    // All of it sits in the SYNC exit, once per acquisition; the decode rounds do not know about it.
+    constexpr bool kSyncStop = !SKIP && LD == 3 && (SF == 7 || SF == 8);
+    if constexpr (kSyncStop) {
+        if (t0) {
+            W.ph_succ = (C.sync_pos && job.sync_succ - 1u < C.n_jobs) ? job.sync_succ : 0u; // (checked here: the SYNC exit keeps no launch parameter alive but the array)
+            if (C.sync_clear) C.sync_clear[jid] = 0ull; // the word this job number publishes in next time
+        }
+    }
     if (t0 && C.balance) {
         const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
         const uint32_t cu = ((xcc & 7u) << 8) | ((hw >> 8) & 0xffu);
@@ -839,6 +850,26 @@ __device__ __forceinline__ void walker2_body(const DevParams &P, const LaunchCfg
                 W2Plan np;
                 plan_from(L, np);
                 next = np; S = L;
+                // (behind the hand-over, and on the state in LDS: a stop written into the register copy ahead of plan_from cost the SF8 kernel 60 more spilled registers)
+                if constexpr (kSyncStop) {
+                    if (C.sync_pos && L.n_att == 0u) { // the first attempt of the job proper / of its probe: no failed attempt, no second trigger before it
+                        const unsigned long long mine = (unsigned long long)(L.pos + 1); // (never zero: zero is "not there yet")
+                        if (phase == 0) {
+                            if (!job.start_at_header) {
+                                // relaxed, like the balance words: the word is all there is to hand over, and an agent-scope store goes through to where every XCD sees it.
+                                // (With a release behind it and an acquire on the reading side - an L2 write-back per job and an L2 invalidate per probe - every round of
+                                // every workgroup paid: SYNC 122 -> 140 k clocks per job, FIND_SFD rounds 33 -> 41 k, the pass 2 % SLOWER than without the early stop.)
+                                __hip_atomic_store(C.sync_pos + jid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        } else {
+                            const uint32_t succ = W.ph_succ; // (0: none; an index inside this launch otherwise)
+                            // one look, no waiting: a successor that has not left SYNC yet, or left it elsewhere, and the probe runs on to the header
+                            if (succ != 0u && __hip_atomic_load(C.sync_pos + (succ - 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == mine) {
+                                S.stop_reason = (int32_t)kStopAtSync; S.done = 1; next.mode = kPlanExit; // (the epilogue reports the attempt as the out-of-data path does)
+                            }
+                        }
+                    }
+                }
             }
             if constexpr (ALIAS) { // the twiddle block back over SYNC's work areas (visible behind the next round's barrier)
                 __syncthreads();
@@ -1098,7 +1129,7 @@ __device__ __forceinline__ void walker2_body(const DevParams &P, const LaunchCfg
             jr.pad = e_pad;
             jr.tail_valid = 0;
             go = job.probe_limit > job.scan_limit && S.stop_reason == 0 && !in_attempt && !trace && e_natt < C.recs_per_job;
-            W.ph_go = go ? 1u : 0u; W.ph_start = e_pos; W.ph_cr = S.cr; W.ph_natt = e_natt; W.ph_pad = 0;
+            W.ph_go = go ? 1u : 0u; W.ph_start = e_pos; W.ph_cr = S.cr; W.ph_natt = e_natt;
         } else {
             jr.tail_valid = 1; jr.tail_first_rec = W.ph_natt;
             jr.tail_final_pos = e_pos; jr.tail_n_attempts = e_natt; jr.tail_final_cr = S.cr; jr.tail_npush = e_npush;

@@ -329,6 +329,10 @@ lora_hip_status lora_hip_last_payload_pass(const lora_hip_decoder_t *h, uint32_t
  * in the gaps between bursts found by the energy-envelope pre-pass, 0 for the fixed grid (configured segment length,
  * sparse or weak traffic, tracing); *segments = segments = workgroups of the main launch.                      */
 lora_hip_status lora_hip_last_plan(const lora_hip_decoder_t *h, uint32_t *burst_aware, uint32_t *segments);
+/* Tail probes of the last pass's main launch (diagnostics): *tail_probes = segment jobs that went on past their cut and reached a packet there,
+ * *at_sync = those of them that ended at their first SYNC exit because the next segment's job had left SYNC at the same sample (SF7 / SF8 at
+ * decimation 8; always 0 elsewhere, under tracing and with LORA_HIP_NO_SYNC_STOP=1).                                                        */
+lora_hip_status lora_hip_last_sync_stops(const lora_hip_decoder_t *h, uint32_t *tail_probes, uint32_t *at_sync);
 /* The handle's ideal-chirp tables (diagnostics; ABI 4): what build_ideal_chirps (decoder_impl.cc:141-175) leaves in d_downchirp (which = 0, 2 sps floats:
  * re, im), d_upchirp (1, 2 sps floats), d_downchirp_ifreq (2, sps floats), d_upchirp_ifreq (3, sps floats) and d_upchirp_ifreq_v (4, 3 sps floats, followed
  * by this library's guard tail of 4 D + 8 copies of the last value: the reference indexes past the vector for bin_idx = N - 1, :301,:310).  Tables 0, 2, 3, 4
