@@ -79,7 +79,15 @@ EXPORTS_RESAMPLER = [
     "lora_hip_resampler_reset", "lora_hip_resampler_last_kernel_ms",
 ]
 
+EXPORTS_CONDITIONER = [
+    "lora_hip_conditioner_create", "lora_hip_conditioner_destroy", "lora_hip_conditioner_last_error", "lora_hip_conditioner_output_items",
+    "lora_hip_conditioner_get_plan", "lora_hip_conditioner_run_device", "lora_hip_conditioner_run_device_raw", "lora_hip_conditioner_work",
+    "lora_hip_conditioner_work_raw", "lora_hip_conditioner_flush_device", "lora_hip_conditioner_flush", "lora_hip_conditioner_reset",
+    "lora_hip_conditioner_set_fixed", "lora_hip_conditioner_set_adaptive", "lora_hip_conditioner_block_records", "lora_hip_conditioner_last_kernel_ms",
+]
+
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
+CONDITIONER_FLAG_DC, CONDITIONER_FLAG_IQ = 1, 2   # include/lora_hip_conditioner.h
 SPECTRUM_WINDOW_HANN, SPECTRUM_WINDOW_RECT = 0, 1   # include/lora_hip_spectrum.h
 SPECTRUM_FLAG_PEAK = 1
 GATEWAY_MAX_DECODERS = 7      # include/lora_hip_gateway.h
@@ -100,6 +108,10 @@ class SpectrumConfig(C.Structure):
 class ResamplerConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("interpolation", C.c_uint32), ("decimation", C.c_uint32), ("zero_crossings", C.c_uint32),
                 ("beta", C.c_double), ("cutoff", C.c_double), ("device", C.c_int32), ("flags", C.c_uint32)]
+
+
+class ConditionerConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("block", C.c_uint32), ("window", C.c_uint32), ("flags", C.c_uint32), ("device", C.c_int32)]
 
 
 class ChannelizerConfig(C.Structure):
@@ -424,6 +436,28 @@ def load():
         L.lora_hip_resampler_reset.argtypes = [vp]
         L.lora_hip_resampler_last_kernel_ms.argtypes = [vp]
         L.lora_hip_resampler_last_kernel_ms.restype = C.c_float
+    if hasattr(L, "lora_hip_conditioner_create") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        u32p, u64p, szp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.lora_hip_conditioner_create.argtypes = [C.POINTER(ConditionerConfig), C.POINTER(vp)]
+        L.lora_hip_conditioner_destroy.argtypes = [vp]
+        L.lora_hip_conditioner_destroy.restype = None
+        L.lora_hip_conditioner_last_error.argtypes = [vp]
+        L.lora_hip_conditioner_last_error.restype = C.c_char_p
+        L.lora_hip_conditioner_output_items.argtypes = [vp, C.c_size_t]
+        L.lora_hip_conditioner_output_items.restype = C.c_size_t
+        L.lora_hip_conditioner_get_plan.argtypes = [vp, u32p, u32p, u32p, u32p]
+        L.lora_hip_conditioner_run_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_conditioner_run_device_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_conditioner_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, szp, u64p]
+        L.lora_hip_conditioner_work_raw.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_float, vp, C.c_size_t, szp, u64p]
+        L.lora_hip_conditioner_flush_device.argtypes = [vp, vp, C.c_size_t, szp, u64p, vp]
+        L.lora_hip_conditioner_flush.argtypes = [vp, vp, C.c_size_t, szp, u64p]
+        L.lora_hip_conditioner_reset.argtypes = [vp]
+        L.lora_hip_conditioner_set_fixed.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+        L.lora_hip_conditioner_set_adaptive.argtypes = [vp]
+        L.lora_hip_conditioner_block_records.argtypes = [vp, vp, vp, C.c_size_t, szp, vp, vp]
+        L.lora_hip_conditioner_last_kernel_ms.argtypes = [vp]
+        L.lora_hip_conditioner_last_kernel_ms.restype = C.c_float
     _lib = L
     return L
 
@@ -1374,3 +1408,124 @@ class Tx:
             self.h = None
 
     __del__ = close
+
+
+class Conditioner:
+    """lora_hip_conditioner_* (include/lora_hip_conditioner.h): DC-offset removal and IQ-imbalance correction, cf32 out at the
+    input's rate.  gr_lora_amd.conditioner.condition is the definition."""
+
+    def __init__(self, block=4096, window=16, dc=True, iq=True, device=0):
+        self.L = load()
+        flags = (CONDITIONER_FLAG_DC if dc else 0) | (CONDITIONER_FLAG_IQ if iq else 0)
+        cfg = ConditionerConfig(struct_size=C.sizeof(ConditionerConfig), block=int(block), window=int(window), flags=flags, device=int(device))
+        self.h = C.c_void_p()
+        st = self.L.lora_hip_conditioner_create(C.byref(cfg), C.byref(self.h))
+        if st != 0:
+            raise LoraHipError(st, self.L.lora_hip_strerror(st).decode())
+        self._held = 0                                 # items waiting for their block: what went in less what came out
+
+    def _check(self, st):
+        if st != 0:
+            raise LoraHipError(st, (self.L.lora_hip_conditioner_last_error(self.h) or b"").decode() or self.L.lora_hip_strerror(st).decode())
+
+    def plan(self) -> Tuple[int, int, int, int]:
+        """The launch plan (lora_hip_conditioner_get_plan): block, window, blocks_per_group, items_per_group."""
+        b, w, g, i = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self.L.lora_hip_conditioner_get_plan(self.h, C.byref(b), C.byref(w), C.byref(g), C.byref(i)))
+        return int(b.value), int(w.value), int(g.value), int(i.value)
+
+    def output_items(self, n_in: int) -> int:
+        return int(self.L.lora_hip_conditioner_output_items(self.h, int(n_in)))
+
+    def work(self, x, max_out=None):
+        """Host buffers: complex64[n_in] -> (complex64[n_out], absolute index of the first output)."""
+        a = np.ascontiguousarray(x, dtype=np.complex64)
+        cap = self.output_items(a.size) if max_out is None else int(max_out)
+        y = np.zeros(max(cap, 1), dtype=np.complex64)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_work(self.h, a.ctypes.data, a.size, y.ctypes.data, cap, C.byref(n), C.byref(first)))
+        self._held += a.size - n.value
+        return y[:n.value], int(first.value)
+
+    def work_raw(self, raw, fmt=None, scale: float = 0.0, max_out=None):
+        """Integer items in (flat interleaved or (n, 2); fmt None: from the dtype); output as work()."""
+        a, f, n_items = _raw_items(raw, fmt)
+        cap = self.output_items(n_items) if max_out is None else int(max_out)
+        y = np.zeros(max(cap, 1), dtype=np.complex64)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_work_raw(self.h, a.ctypes.data, n_items, f, float(scale), y.ctypes.data, cap, C.byref(n), C.byref(first)))
+        self._held += n_items - n.value
+        return y[:n.value], int(first.value)
+
+    def run_device(self, d_in: int, n_in: int, d_out: int, max_out: int, stream: int = 0):
+        """-> (outputs written, absolute index of the first of them)."""
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_run_device(self.h, d_in, int(n_in), d_out, int(max_out), C.byref(n), C.byref(first), stream))
+        self._held += int(n_in) - n.value
+        return int(n.value), int(first.value)
+
+    def run_device_raw(self, d_in: int, n_in: int, fmt: int, d_out: int, max_out: int, scale: float = 0.0, stream: int = 0):
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_run_device_raw(self.h, d_in, int(n_in), int(fmt), float(scale), d_out, int(max_out), C.byref(n),
+                                                               C.byref(first), stream))
+        self._held += int(n_in) - n.value
+        return int(n.value), int(first.value)
+
+    def held_items(self) -> int:
+        """Items held back for the next block (what flush would emit)."""
+        return self._held
+
+    def flush(self):
+        """-> (the held items, corrected with the newest parameters; absolute index of the first of them)."""
+        cap = self.held_items()
+        y = np.zeros(max(cap, 1), dtype=np.complex64)
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_flush(self.h, y.ctypes.data, cap, C.byref(n), C.byref(first)))
+        self._held -= n.value
+        return y[:n.value], int(first.value)
+
+    def flush_device(self, d_out: int, max_out: int, stream: int = 0):
+        n, first = C.c_size_t(0), C.c_uint64(0)
+        self._check(self.L.lora_hip_conditioner_flush_device(self.h, d_out, int(max_out), C.byref(n), C.byref(first), stream))
+        self._held -= n.value
+        return int(n.value), int(first.value)
+
+    def block_records(self):
+        """-> (moments float64[n, 5], params float32[n, 4]) of the blocks the last run call completed."""
+        n = C.c_size_t(0)
+        self._check(self.L.lora_hip_conditioner_block_records(self.h, None, None, 0, C.byref(n), None, None))
+        mom, par = np.zeros((n.value, 5), dtype=np.float64), np.zeros((n.value, 4), dtype=np.float32)
+        if n.value:
+            self._check(self.L.lora_hip_conditioner_block_records(self.h, mom.ctypes.data, par.ctypes.data, n.value, C.byref(n), None, None))
+        return mom, par
+
+    def newest(self):
+        """-> (params float32[4]: dI, dQ, a, b; estimates float64[4]: mI, mQ, r, q) of the newest complete block."""
+        n = C.c_size_t(0)
+        par, est = np.zeros(4, dtype=np.float32), np.zeros(4, dtype=np.float64)
+        self._check(self.L.lora_hip_conditioner_block_records(self.h, None, None, 0, C.byref(n), par.ctypes.data, est.ctypes.data))
+        return par, est
+
+    def set_fixed(self, d_i, d_q, a, b):
+        self._check(self.L.lora_hip_conditioner_set_fixed(self.h, float(d_i), float(d_q), float(a), float(b)))
+
+    def set_adaptive(self):
+        self._check(self.L.lora_hip_conditioner_set_adaptive(self.h))
+
+    def reset(self):
+        self._check(self.L.lora_hip_conditioner_reset(self.h))
+        self._held = 0
+
+    def kernel_ms(self) -> float:
+        return float(self.L.lora_hip_conditioner_last_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.lora_hip_conditioner_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -20,6 +20,8 @@ Same names, argument order and meaning as the reference module `lora`:
   lora.rational_resampler(in_rate, out_rate, zero_crossings, beta, cutoff)
                                               (not upstream, which leaves it to a GNU Radio block: rate in_rate -> in_rate * L / M on
                                               the device, in front of any receiver, for captures at 2.4, 2.048, 1.92 ... Msps)
+  lora.iq_conditioner(block, window, dc, iq)  (not upstream: removes a direct-conversion front end's DC offset and IQ imbalance on the
+                                              device, estimated from block moments; the first stage, in front of the resampler)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -699,6 +701,96 @@ class rational_resampler:
 
     def reset(self):
         """Drops the carried items: the next item is sample 0 of a new stream."""
+        self._h.reset()
+
+    def kernel_ms(self) -> float:
+        return self._h.kernel_ms()
+
+    def close(self):
+        self._h.close()
+
+
+class iq_conditioner:
+    """The first stage for a capture from a direct-conversion front end (include/lora_hip_conditioner.h, csrc/lora_conditioner.hip):
+    removes the DC offset and corrects the gain / phase mismatch between I and Q, both estimated over the last `window` blocks of
+    `block` items, on the device, in any chunking.  cf32 out at the input's rate, item for item; up to block - 1 items wait for
+    their block to complete (flush() emits them).  gr_lora_amd.conditioner.condition is the definition.  No host fall-back."""
+
+    def __init__(self, block=4096, window=16, dc=True, iq=True, device=0):
+        self.block, self.window, self.dc, self.iq = int(block), int(window), bool(dc), bool(iq)
+        self.device = int(device)
+        self._h = capi.Conditioner(self.block, self.window, self.dc, self.iq, self.device)
+        self._last_device = None                      # the device of the last device tensor: flush() answers in kind
+
+    def work(self, input_items, scale=0):
+        """numpy complex64 (host), or a torch CUDA tensor (complex64, or float32 interleaved) read on the current stream; or integer
+        IQ: a numpy array or a torch CUDA tensor of dtype int16 / int8 / uint8, flat interleaved or (n, 2), with an optional scale.
+        -> the complex64 items of the blocks these items complete: a numpy array for host input, a CUDA tensor written on the
+        current stream for device input."""
+        x = input_items
+        if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            t = x.contiguous()
+            if t.device.index != self.device:
+                raise ValueError("iq_conditioner.work: the tensor is on %s, the conditioner on cuda:%d" % (t.device, self.device))
+            fmt = {torch.int16: iqformat.SC16, torch.int8: iqformat.SC8, torch.uint8: iqformat.CU8}.get(t.dtype)
+            if fmt is not None:
+                if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 2)) or t.numel() % 2:
+                    raise ValueError("iq_conditioner.work: integer IQ must be flat interleaved pairs or shaped (n, 2), not %s" % (tuple(t.shape),))
+                n = t.numel() // 2
+                sc = iqformat.check_scale(scale)
+            else:
+                if scale:
+                    raise TypeError("iq_conditioner.work: scale applies to integer IQ, not to %s" % t.dtype)
+                if t.dtype == torch.complex64:
+                    n = t.numel()
+                elif t.dtype == torch.float32:
+                    if t.numel() % 2:
+                        raise ValueError("iq_conditioner.work: a float32 tensor holds interleaved I/Q pairs, not %d floats" % t.numel())
+                    n = t.numel() // 2
+                else:
+                    raise TypeError("iq_conditioner.work: a device tensor must be complex64 or float32 interleaved, not %s" % t.dtype)
+            cap = self._h.output_items(n)
+            y = torch.empty(max(cap, 1), dtype=torch.complex64, device=t.device)
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+            if fmt is not None:
+                got, _first = self._h.run_device_raw(t.data_ptr(), n, fmt, y.data_ptr(), cap, sc, stream)
+            else:
+                got, _first = self._h.run_device(t.data_ptr(), n, y.data_ptr(), cap, stream)
+            self._last_device = t.device
+            return y[:got]
+        self._last_device = None
+        raw = _integer_iq(x, scale)
+        if raw is not None:
+            return self._h.work_raw(raw[0], raw[1], scale)[0]
+        return self._h.work(np.asarray(x, dtype=np.complex64))[0]
+
+    def flush(self):
+        """The held items, corrected with the newest block's parameters: a CUDA tensor if the last work() took one, else numpy."""
+        if self._last_device is not None:
+            import torch
+            cap = self._h.held_items()
+            y = torch.empty(max(cap, 1), dtype=torch.complex64, device=self._last_device)
+            got, _first = self._h.flush_device(y.data_ptr(), cap, torch.cuda.current_stream(self._last_device).cuda_stream)
+            return y[:got]
+        return self._h.flush()[0]
+
+    def estimate(self) -> dict:
+        """What the newest block's window says about the front end: dc (complex), dc_dbfs (|dc| against full scale 1.0), gain_db and
+        phase_deg of the I/Q mismatch (g = sqrt(q), phi = asin(r / sqrt(q)), formed here from the device's fp64 estimates)."""
+        from . import conditioner
+        _par, est = self._h.newest()
+        return conditioner.mismatch(*est)
+
+    def set_fixed(self, d_i, d_q, a, b):
+        """Calibrated constants instead of estimates: zI = I - d_i, zQ = a zI + b (Q - d_q)."""
+        self._h.set_fixed(d_i, d_q, a, b)
+
+    def set_adaptive(self):
+        self._h.set_adaptive()
+
+    def reset(self):
+        """Drops the held items and the window: the next item is sample 0 of a new stream."""
         self._h.reset()
 
     def kernel_ms(self) -> float:
