@@ -9,12 +9,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "liblora_hip.so")
 SOURCES = ["lora_kernels.hip", "lora_runtime.cpp", "lora_channelizer.hip", "lora_filterbank.hip", "lora_iq_unpack.hip", "lora_gateway.cpp", "lora_frame_check.cpp", "lora_tx.hip", "lora_link.hip", "lora_spectrum.hip", "lora_resampler.hip", "lora_conditioner.hip"]
-DEPS = SOURCES + ["lora_device.h", "lora_stitch.hpp", "lora_walker2.inc.hip", "lora_walker3.inc.hip", "lora_team_demod.inc.hip", "lora_wave_demod.inc.hip", "lora_wave_decim.inc.hip", "lora_detect.inc.hip", "lora_strict_sync.inc.hip", "lora_strict_resolve_lds.inc", "whitening_data.inc", "lora_mux_dev.h", "lora_iq.h", "lora_frame_check.h", "lora_link.h",
+DEPS = SOURCES + ["lora_device.h", "lora_stitch.hpp", "lora_walker2.inc.hip", "lora_walker3.inc.hip", "lora_team_demod.inc.hip", "lora_wave_demod.inc.hip", "lora_wave_decim.inc.hip", "lora_detect.inc.hip", "lora_soft.inc.hip", "lora_strict_sync.inc.hip", "lora_strict_resolve_lds.inc", "whitening_data.inc", "lora_mux_dev.h", "lora_iq.h", "lora_frame_check.h", "lora_link.h",
                   os.path.join("..", "..", "include", "lora_hip.h"), os.path.join("..", "..", "include", "lora_hip_channelizer.h"),
                   os.path.join("..", "..", "include", "lora_hip_filterbank.h"), os.path.join("..", "..", "include", "lora_hip_gateway.h"),
                   os.path.join("..", "..", "include", "lora_hip_tx.h"), os.path.join("..", "..", "include", "lora_hip_link.h"),
                   os.path.join("..", "..", "include", "lora_hip_spectrum.h"), os.path.join("..", "..", "include", "lora_hip_resampler.h"),
-                  os.path.join("..", "..", "include", "lora_hip_conditioner.h")]
+                  os.path.join("..", "..", "include", "lora_hip_conditioner.h"), os.path.join("..", "..", "include", "lora_hip_soft.h")]
 
 
 CODEGEN_FLAGS = ["-mllvm", "-greedy-reverse-local-assignment"]

@@ -86,6 +86,10 @@ EXPORTS_CONDITIONER = [
     "lora_hip_conditioner_set_fixed", "lora_hip_conditioner_set_adaptive", "lora_hip_conditioner_block_records", "lora_hip_conditioner_last_kernel_ms",
 ]
 
+EXPORTS_SOFT = ["lora_hip_soft_symbols_device", "lora_hip_soft_decode_at_headers_device"]
+
+SOFT_REQUIRE_HEADER_CHECKSUM = 1   # include/lora_hip_soft.h
+SOFT_FRAME, SOFT_HEADER_REJECTED, SOFT_CR_ZERO, SOFT_TRUNCATED = 0, 1, 2, 3   # lora_hip_soft_report_t.status
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
 CONDITIONER_FLAG_DC, CONDITIONER_FLAG_IQ = 1, 2   # include/lora_hip_conditioner.h
 SPECTRUM_WINDOW_HANN, SPECTRUM_WINDOW_RECT = 0, 1   # include/lora_hip_spectrum.h
@@ -165,6 +169,15 @@ class WindowStats(C.Structure):
 class Preamble(C.Structure):
     _fields_ = [("header_pos", C.c_int64), ("run_pos", C.c_int64), ("stream", C.c_uint32), ("run_len", C.c_uint32), ("bin", C.c_int32), ("sfd_index", C.c_int32),
                 ("pmr", C.c_float), ("cfo_bins", C.c_float), ("cfo_hz", C.c_float), ("delta", C.c_int32)]
+
+
+class SoftReport(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("cr", C.c_uint32), ("payload_length", C.c_uint32), ("payload_symbols", C.c_uint32),
+                ("header_checksum_ok", C.c_uint8), ("has_crc", C.c_uint8), ("crc_ok", C.c_uint8), ("reserved", C.c_uint8),
+                ("codewords", C.c_uint32), ("changed", C.c_uint32), ("min_margin", C.c_float), ("mean_abs_llr", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _t in self._fields_ if k != "reserved"}
 
 
 class GatewayConfig(C.Structure):
@@ -458,6 +471,10 @@ def load():
         L.lora_hip_conditioner_block_records.argtypes = [vp, vp, vp, C.c_size_t, szp, vp, vp]
         L.lora_hip_conditioner_last_kernel_ms.argtypes = [vp]
         L.lora_hip_conditioner_last_kernel_ms.restype = C.c_float
+    if hasattr(L, "lora_hip_soft_symbols_device") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        L.lora_hip_soft_symbols_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        L.lora_hip_soft_decode_at_headers_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.POINTER(Preamble), C.c_size_t, C.c_uint32,
+                                                             C.POINTER(SoftReport), vp]
     _lib = L
     return L
 
@@ -505,6 +522,7 @@ class Handle:
         self.L.lora_hip_get_geometry(self.h, C.byref(a), C.byref(b), C.byref(d))
         self.sps, self.nbins, self.decim = a.value, b.value, d.value
         self.device, self.batch_items = int(device), int(batch_items)
+        self.reduced_rate = bool(reduced_rate)
 
     def close(self):
         if getattr(self, "h", None):
@@ -644,6 +662,40 @@ class Handle:
             st, hp = (p["stream"], p["header_pos"]) if isinstance(p, dict) else p
             arr[i].stream, arr[i].header_pos = int(st), int(hp)
         self._check(self.L.lora_hip_decode_at_headers_device(self.h, dev_ptr, total_items, o.ctypes.data, l.ctypes.data, o.size, arr, len(preambles), stream))
+
+    def soft_symbols_device(self, dev_ptr: int, total_items: int, offsets: Sequence[int], reduced=None, stream: int = 0):
+        """lora_hip_soft_symbols_device: (list of per-window LLR arrays - sf - 2 floats where reduced[i], else sf -, arg-max indices k, peak
+        magnitudes).  reduced None: the handle's reduced_rate for every window."""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        red = None if reduced is None else np.ascontiguousarray(np.asarray(reduced) != 0, dtype=np.uint8)
+        if red is not None and red.size != off.size:
+            raise ValueError("one reduced flag per window")
+        llr = np.zeros(max(off.size, 1) * 12, dtype=np.float32)
+        k = np.zeros(max(off.size, 1), dtype=np.int32)
+        peak = np.zeros(max(off.size, 1), dtype=np.float32)
+        self._check(self.L.lora_hip_soft_symbols_device(self.h, dev_ptr, total_items, off.ctypes.data, off.size, None if red is None else red.ctypes.data,
+                                                        llr.ctypes.data, k.ctypes.data, peak.ctypes.data, stream))
+        sf = int(self.nbins).bit_length() - 1
+        out, at = [], 0
+        for i in range(off.size):
+            ppm = sf - 2 if (self.reduced_rate if red is None else red[i]) else sf
+            out.append(llr[at:at + ppm].copy())
+            at += ppm
+        return out, k[: off.size], peak[: off.size]
+
+    def soft_decode_at_headers_device(self, dev_ptr: int, total_items: int, offs: Sequence[int], lens: Sequence[int], preambles, flags: int = 0, stream: int = 0):
+        """lora_hip_soft_decode_at_headers_device: decode_at_headers_device with soft decisions; frames go to the handle's queue (drain them as
+        before), the per-entry reports come back as dicts."""
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        l = np.ascontiguousarray(lens, dtype=np.uint64)
+        arr = (Preamble * max(len(preambles), 1))()
+        for i, p in enumerate(preambles):
+            st, hp = (p["stream"], p["header_pos"]) if isinstance(p, dict) else p
+            arr[i].stream, arr[i].header_pos = int(st), int(hp)
+        rep = (SoftReport * max(len(preambles), 1))()
+        self._check(self.L.lora_hip_soft_decode_at_headers_device(self.h, dev_ptr, total_items, o.ctypes.data, l.ctypes.data, o.size, arr, len(preambles), int(flags),
+                                                                  rep, stream))
+        return [r.as_dict() for r in rep[: len(preambles)]]
 
     def frames_available(self) -> int:
         return self.L.lora_hip_frames_available(self.h)

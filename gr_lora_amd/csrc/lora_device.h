@@ -22,6 +22,30 @@ constexpr int kMaxBinsPerThread = 16; // N / kWG at SF12
 constexpr int kMaxFrame = 3 + 255 + 2;
 constexpr int kMaxCodewords = 640;    // (sf-7) + ceil(2*257/ppm)*ppm  <= 5 + 44*12
 
+// The Hamming(8,4) code of hamming_encode_soft (include/lora/utilities.h:257-264), and its nearest-codeword table (ties, from two bit errors on:
+// the lowest symbol; liquid's choice in fec_decode is unpinned): the one statement of both for host and device code.
+#if defined(__HIPCC__)
+#define LORA_HIP_HD __host__ __device__
+#else
+#define LORA_HIP_HD
+#endif
+LORA_HIP_HD inline uint32_t hamming84_encode(uint32_t v)
+{
+    const uint32_t b0 = v & 1u, b1 = (v >> 1) & 1u, b2 = (v >> 2) & 1u, b3 = (v >> 3) & 1u;
+    return (b1 ^ b2 ^ b3) | (b0 << 1) | (b1 << 2) | (b2 << 3) | ((b0 ^ b1 ^ b2) << 4) | (b3 << 5) | ((b0 ^ b1 ^ b3) << 6) | ((b0 ^ b2 ^ b3) << 7);
+}
+inline void hamming84_decode_table(unsigned char (&dec)[256])
+{
+    for (uint32_t cw = 0; cw < 256u; cw++) {
+        int best = 0, best_d = 9;
+        for (uint32_t s = 0; s < 16u; s++) {
+            const int d = __builtin_popcount(cw ^ hamming84_encode(s));
+            if (d < best_d) { best_d = d; best = (int)s; }
+        }
+        dec[cw] = (unsigned char)best;
+    }
+}
+
 enum DecState : int32_t { kDetect = 0, kSync, kFindSfd, kPause, kDecodeHeader, kDecodePayload, kStop };
 
 enum AttemptStatus : uint32_t {
@@ -239,5 +263,27 @@ uint32_t walker_lds_bytes(const DevParams &p);
 uint32_t walker_resident_slots(const DevParams &p);
 uint32_t walker_resident_slots_full(const DevParams &p);                  // second, smaller slot count where the kernel exists as half- and full-size workgroups (0: none)
 const char *walker_kernel_name_for(const DevParams &p, uint32_t n_jobs, bool skip = false); // ... and the variant a launch of n_jobs jobs runs (skip: LaunchCfg.skip_payload)
+
+// Soft-decision decoding at known header positions (lora_soft.inc.hip; include/lora_hip_soft.h).
+constexpr uint32_t kSoftStride = 12; // floats per window in a device LLR buffer (ppm <= 12; entries past a window's ppm are 0)
+struct SoftSym { int32_t k; float peak; }; // per window: arg-max index (k mod N) and its magnitude
+struct SoftFrameDesc { // one frame in one launch of soft_chain_kernel (host-written)
+    uint32_t hdr_win;  // its eight header windows in the header LLR buffer
+    uint32_t pay_win;  // its first payload window in the payload LLR buffer
+    uint32_t first_x;  // codeword of the header block that is codeword 0 of this launch: 0 (the five header codewords) or 5 (the spare ones)
+    uint32_t n_first;  // codewords taken from the header block: 5, or sf - 7
+    uint32_t n_cw;     // n_first + payload blocks * ppm
+    uint32_t n_w;      // words of a payload block: 4 + cr
+    uint32_t ppm;      // bits of a payload word
+    uint32_t table;    // whitening: 0 HEADER, 1 CR56, 2 CR78 (index: the codeword's number in this launch; 0 past the table's end)
+    uint32_t cw_out;   // its first codeword record
+    uint32_t byte_out; // its first assembled byte
+    uint32_t n_bytes;  // bytes to assemble, low nibble first (0 in the header launch: the host builds the three header bytes)
+};
+struct SoftCw { float margin, sum_abs; uint8_t nibble, hard, pad[2]; }; // (device-written) hard: the de-whitened word of the LLR signs
+int launch_soft_symbols(const DevParams &p, const float2 *iq, const int64_t *d_offsets, const uint8_t *d_reduced, uint32_t n, float *d_llr, SoftSym *d_sym, void *stream);
+// frames on grid x, 64 pairs of codewords per workgroup on grid y (max_pairs: the largest max(ceil(n_cw / 2), n_bytes) of the launch)
+int launch_soft_chain(const DevParams &p, const SoftFrameDesc *d_descs, uint32_t n_frames, uint32_t max_pairs, const float *d_llr_hdr, const float *d_llr_pay, SoftCw *d_cws,
+                      uint8_t *d_bytes, void *stream);
 
 } // namespace lora_hip

@@ -21,7 +21,10 @@
 
 #include "../../include/lora_hip.h"
 #include "../../include/lora_hip_link.h"
+#include "../../include/lora_hip_soft.h"
 #include "lora_device.h"
+#include "lora_frame_check.h"
+#include "whitening_data.inc"
 #include "lora_link.h"
 #include "lora_stitch.hpp"
 #include "lora_mux_dev.h"
@@ -235,6 +238,15 @@ struct lora_hip_decoder {
         uint64_t launches = 0, frames = 0;
         double kernel_ms = 0.0;
     } link;
+    // soft-decision decoding (include/lora_hip_soft.h): LLRs of header and payload windows (they stay on the device), what the chain leaves
+    struct Soft {
+        DevBuf<float> d_llr_hdr, d_llr_pay;
+        DevBuf<uint8_t> d_reduced, d_bytes;
+        DevBuf<SoftSym> d_sym;
+        DevBuf<SoftFrameDesc> d_descs;
+        DevBuf<SoftCw> d_cws;
+        void release() { d_llr_hdr.release(); d_llr_pay.release(); d_reduced.release(); d_bytes.release(); d_sym.release(); d_descs.release(); d_cws.release(); }
+    } soft;
     struct PayState { std::vector<uint32_t> active; size_t used = 0, cap_sym = 0, n_sym = 0; int round = 0; float ms = 0.0f; bool open = false; } pay;
 };
 
@@ -1371,6 +1383,7 @@ void lora_hip_destroy(lora_hip_decoder_t *h)
     h->p_pay_off.release(); h->p_pay_desc.release(); h->p_pay_out.release(); h->d_fine.release(); h->d_alt_shift.release(); h->d_alt_bins.release(); h->d_alt_fine.release();
     h->d_jobs.release(); h->d_results.release(); h->d_recs.release(); h->d_scratch.release();
     h->d_trace.release(); h->d_staging.release(); h->d_offsets.release(); h->d_bins.release();
+    h->soft.release();
     for (auto &r : h->feed.pinned) (void)hipHostUnregister((void *)r.first);
     for (int i = 0; i < 2; i++) { h->pipe.dbuf[i].release(); h->feed.stage[i].release(); }
     h->feed.d_raw.release();
@@ -2357,6 +2370,191 @@ lora_hip_status lora_hip_link_stats(const lora_hip_decoder_t *h, uint64_t *launc
     if (launches) *launches = h->link.launches;
     if (frames) *frames = h->link.frames;
     if (kernel_ms) *kernel_ms = h->link.kernel_ms;
+    return LORA_HIP_OK;
+}
+
+// ---- soft-decision decoding at known header positions (include/lora_hip_soft.h; definition: gr_lora_amd/softdecode.py) ----------
+// the LLRs of the windows at offs (items into d_iq) into llr, kSoftStride floats each, and their records into soft.d_sym; queued on st, not awaited
+static lora_hip_status soft_llrs(lora_hip_decoder_t *h, const float2 *d_iq, const std::vector<int64_t> &offs, const std::vector<uint8_t> &red, DevBuf<float> &llr, hipStream_t st)
+{
+    const size_t n = offs.size();
+    HIP_TRY(h, h->d_offsets.reserve(n));
+    HIP_TRY(h, h->soft.d_reduced.reserve(n));
+    HIP_TRY(h, h->soft.d_sym.reserve(n));
+    HIP_TRY(h, llr.reserve(n * kSoftStride));
+    HIP_TRY(h, hipMemcpyAsync(h->d_offsets.p, offs.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->soft.d_reduced.p, red.data(), n, hipMemcpyHostToDevice, st));
+    if (launch_soft_symbols(h->P, d_iq, h->d_offsets.p, h->soft.d_reduced.p, (uint32_t)n, llr.p, h->soft.d_sym.p, st) != 0)
+        return fail(h, LORA_HIP_ERR_HIP, "soft symbols launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_soft_symbols_device(lora_hip_decoder_t *h, const void *d_iq, size_t total_items, const int64_t *offsets, size_t n,
+                                             const uint8_t *reduced, float *llr_out, int32_t *k_out, float *peak_out, void *hip_stream)
+{
+    if (!h || !d_iq || (n && (!offsets || !llr_out)) || n > 0x7fffffffu / kSoftStride) return LORA_HIP_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i] < 0 || (uint64_t)offsets[i] + h->P.sps > total_items) return fail(h, LORA_HIP_ERR_ARG, "window %zu out of range", i);
+    if (n == 0) return LORA_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<int64_t> offs(offsets, offsets + n);
+    std::vector<uint8_t> red(n, (uint8_t)(h->P.reduced_rate ? 1 : 0));
+    if (reduced) for (size_t i = 0; i < n; i++) red[i] = reduced[i] ? 1 : 0;
+    const lora_hip_status rc = soft_llrs(h, (const float2 *)d_iq, offs, red, h->soft.d_llr_pay, st);
+    if (rc != LORA_HIP_OK) return rc;
+    std::vector<float> L(n * kSoftStride);
+    std::vector<SoftSym> S(n);
+    HIP_TRY(h, hipMemcpyAsync(L.data(), h->soft.d_llr_pay.p, L.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(S.data(), h->soft.d_sym.p, n * sizeof(SoftSym), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t ppm = red[i] ? h->P.sf - 2u : h->P.sf;
+        std::copy(L.begin() + i * kSoftStride, L.begin() + i * kSoftStride + ppm, llr_out + at);
+        at += ppm;
+        if (k_out) k_out[i] = S[i].k;
+        if (peak_out) peak_out[i] = S[i].peak;
+    }
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, const void *d_iq, size_t total_items, const uint64_t *stream_off,
+                                                       const uint64_t *stream_len, uint32_t n_streams, const lora_hip_preamble_t *pre, size_t n,
+                                                       uint32_t flags, lora_hip_soft_report_t *reports, void *hip_stream)
+{
+    if (!h || !d_iq || !n_streams || !stream_off || !stream_len || (n && !pre) || (flags & ~LORA_HIP_SOFT_REQUIRE_HEADER_CHECKSUM)) return LORA_HIP_ERR_ARG;
+    if (h->pass_open) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_soft_decode_at_headers_device: a pass is open on this handle");
+    if (h->P.implicit) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "decode at given headers needs an explicit header");
+    if (h->P.sf < 7u) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "soft decoding needs sf >= 7: the header block of an explicit header holds 5 codewords, sf - 2 = %u fit", h->P.sf - 2u);
+    if (n == 0) return LORA_HIP_OK;
+    if (n > 0x7fffffffu / (8u * kSoftStride)) return fail(h, LORA_HIP_ERR_ARG, "too many entries for one call");
+    const int64_t sps = h->P.sps;
+    const uint32_t sf = h->P.sf, ppm_h = sf - 2u, ppm_p = h->P.reduced_rate ? sf - 2u : sf, n_spare = sf - 7u;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t s = pre[i].stream;
+        if (s >= n_streams || stream_off[s] > total_items || stream_len[s] > total_items - stream_off[s]) return fail(h, LORA_HIP_ERR_ARG, "entry %zu: bad stream", i);
+        if (pre[i].header_pos < 0 || (uint64_t)pre[i].header_pos + 2u * h->P.sps > stream_len[s]) return fail(h, LORA_HIP_ERR_ARG, "entry %zu: header position outside its stream", i);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->err.clear();
+    hipStream_t st = (hipStream_t)hip_stream;
+    const float2 *iq = (const float2 *)d_iq;
+    static const std::vector<uint8_t> h84 = [] { // the integer chain's nearest-codeword table
+        unsigned char t[256];
+        hamming84_decode_table(t);
+        return std::vector<uint8_t>(t, t + 256);
+    }();
+    struct Ent { lora_hip_soft_report_t rep; uint8_t phdr[3]; bool have_hdr, go; uint32_t slot, taken, desc; double sum_abs; };
+    std::vector<Ent> ent(n, Ent{});
+    // stage 1: the eight header windows of every entry, one launch; their five header codewords, one more; the host reads the headers
+    std::vector<int64_t> offs;
+    std::vector<uint8_t> red;
+    uint32_t n_hdr = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t s = pre[i].stream;
+        ent[i].rep.status = LORA_HIP_SOFT_TRUNCATED;
+        if ((uint64_t)pre[i].header_pos + 9u * (uint64_t)sps > stream_len[s]) continue; // (every symbol needs 2 sps items from its position, :91)
+        ent[i].have_hdr = true; ent[i].slot = n_hdr++;
+        for (int k = 0; k < 8; k++) { offs.push_back((int64_t)stream_off[s] + pre[i].header_pos + k * sps); red.push_back(1); }
+    }
+    std::vector<SoftFrameDesc> descs;
+    std::vector<SoftCw> cws;
+    HIP_TRY(h, h->soft.d_bytes.reserve(16));
+    HIP_TRY(h, h->soft.d_llr_pay.reserve(16));
+    if (n_hdr) {
+        lora_hip_status rc = soft_llrs(h, iq, offs, red, h->soft.d_llr_hdr, st);
+        if (rc != LORA_HIP_OK) return rc;
+        for (uint32_t k = 0; k < n_hdr; k++) descs.push_back(SoftFrameDesc{k * 8u, 0u, 0u, 5u, 5u, 8u, ppm_h, 0u, k * 5u, 0u, 0u});
+        cws.resize((size_t)n_hdr * 5u);
+        HIP_TRY(h, h->soft.d_descs.reserve(descs.size()));
+        HIP_TRY(h, h->soft.d_cws.reserve(cws.size()));
+        HIP_TRY(h, hipMemcpyAsync(h->soft.d_descs.p, descs.data(), descs.size() * sizeof(SoftFrameDesc), hipMemcpyHostToDevice, st));
+        if (launch_soft_chain(h->P, h->soft.d_descs.p, n_hdr, 3u, h->soft.d_llr_hdr.p, h->soft.d_llr_pay.p, h->soft.d_cws.p, h->soft.d_bytes.p, st) != 0)
+            return fail(h, LORA_HIP_ERR_HIP, "soft chain launch failed: %s", hipGetErrorString(hipGetLastError()));
+        HIP_TRY(h, hipMemcpyAsync(cws.data(), h->soft.d_cws.p, cws.size() * sizeof(SoftCw), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    // the headers; stage 2: all payload windows of all frames, one launch; the spare and payload codewords and the bytes, one more
+    offs.clear(); red.clear(); descs.clear();
+    uint32_t n_cw_all = 0, n_bytes_all = 0, max_pairs = 0;
+    for (size_t i = 0; i < n; i++) {
+        Ent &e = ent[i];
+        if (!e.have_hdr) continue;
+        const SoftCw *c = cws.data() + (size_t)e.slot * 5u;
+        lora_hip_soft_report_t &r = e.rep;
+        e.phdr[0] = (uint8_t)((c[0].nibble << 4) | c[1].nibble);
+        e.phdr[1] = (uint8_t)((c[2].nibble << 4) | c[3].nibble);
+        e.phdr[2] = (uint8_t)((c[4].nibble << 4) | h84[LORA_WHITEN_HEADER[5]]); // (decode(true) pads the fifth nibble's byte with a sixth, empty codeword, :633)
+        if ((e.phdr[1] >> 5) > 4) e.phdr[1] = (uint8_t)((e.phdr[1] & 0x1f) | (4u << 5)); // :834-835
+        r.cr = e.phdr[1] >> 5; r.has_crc = (e.phdr[1] >> 4) & 1u;
+        r.payload_length = (uint32_t)e.phdr[0] + 2u * r.has_crc;
+        r.header_checksum_ok = lora_frame::header_checksum(e.phdr[0], r.cr, r.has_crc) == ((((uint32_t)e.phdr[1] << 4) & 0x10u) | (uint32_t)(e.phdr[2] >> 4));
+        r.codewords = 5; r.min_margin = c[0].margin;
+        for (int k = 0; k < 5; k++) { r.changed += c[k].nibble != h84[c[k].hard]; r.min_margin = std::min(r.min_margin, c[k].margin); e.sum_abs += (double)c[k].sum_abs; }
+        if (r.cr == 0) { r.status = LORA_HIP_SOFT_CR_ZERO; continue; }
+        if ((flags & LORA_HIP_SOFT_REQUIRE_HEADER_CHECKSUM) && !r.header_checksum_ok) { r.status = LORA_HIP_SOFT_HEADER_REJECTED; continue; }
+        const int spb = (int)r.cr + 4; // :842-847
+        const float symbols_needed = (float)r.payload_length * 8.0f * ((float)spb / 4.0f) / (float)ppm_p;
+        const uint32_t n_sym = (uint32_t)((int)std::ceil(symbols_needed / (float)spb) * spb);
+        r.payload_symbols = n_sym;
+        e.taken = n_sym ? n_sym : 1u; // (a header that asks for no symbol still takes one, and no block, :866-870)
+        const uint32_t s = pre[i].stream;
+        if ((uint64_t)pre[i].header_pos + (uint64_t)(8u + e.taken + 1u) * (uint64_t)sps > stream_len[s]) continue; // TRUNCATED
+        e.go = true; e.desc = (uint32_t)descs.size();
+        SoftFrameDesc d{e.slot * 8u, (uint32_t)offs.size(), 5u, n_spare, n_spare + (n_sym / (uint32_t)spb) * ppm_p, (uint32_t)spb, ppm_p, r.cr <= 2u ? 1u : 2u, n_cw_all, n_bytes_all, r.payload_length};
+        for (uint32_t k = 0; k < n_sym; k++) { offs.push_back((int64_t)stream_off[s] + pre[i].header_pos + (int64_t)(8u + k) * sps); red.push_back((uint8_t)(h->P.reduced_rate ? 1 : 0)); }
+        n_cw_all += d.n_cw; n_bytes_all += d.n_bytes;
+        max_pairs = std::max(max_pairs, std::max((d.n_cw + 1u) / 2u, d.n_bytes));
+        descs.push_back(d);
+    }
+    std::vector<uint8_t> bytes(n_bytes_all);
+    cws.assign(n_cw_all, SoftCw{});
+    if (!offs.empty()) {
+        const lora_hip_status rc = soft_llrs(h, iq, offs, red, h->soft.d_llr_pay, st);
+        if (rc != LORA_HIP_OK) return rc;
+    }
+    if (!descs.empty() && max_pairs) {
+        HIP_TRY(h, h->soft.d_descs.reserve(descs.size()));
+        HIP_TRY(h, h->soft.d_cws.reserve(n_cw_all + 1u));
+        HIP_TRY(h, h->soft.d_bytes.reserve(n_bytes_all + 1u));
+        HIP_TRY(h, hipMemcpyAsync(h->soft.d_descs.p, descs.data(), descs.size() * sizeof(SoftFrameDesc), hipMemcpyHostToDevice, st));
+        if (launch_soft_chain(h->P, h->soft.d_descs.p, (uint32_t)descs.size(), max_pairs, h->soft.d_llr_hdr.p, h->soft.d_llr_pay.p, h->soft.d_cws.p, h->soft.d_bytes.p, st) != 0)
+            return fail(h, LORA_HIP_ERR_HIP, "soft chain launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (n_cw_all) HIP_TRY(h, hipMemcpyAsync(cws.data(), h->soft.d_cws.p, cws.size() * sizeof(SoftCw), hipMemcpyDeviceToHost, st));
+        if (n_bytes_all) HIP_TRY(h, hipMemcpyAsync(bytes.data(), h->soft.d_bytes.p, bytes.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    // frames, in the order of pre (msg_lora_frame, :588-609; SNR byte 0: no DETECT step fed the power queue)
+    for (size_t i = 0; i < n; i++) {
+        Ent &e = ent[i];
+        lora_hip_soft_report_t &r = e.rep;
+        if (e.go) {
+            const SoftFrameDesc &d = descs[e.desc];
+            const SoftCw *c = cws.data() + d.cw_out;
+            for (uint32_t k = 0; k < d.n_cw; k++) {
+                uint32_t hard_nib = h84[c[k].hard];
+                if (r.cr <= 2u) { const uint32_t w = c[k].hard; hard_nib = ((w >> 1) & 1u) | (((w >> 2) & 1u) << 1) | (((w >> 3) & 1u) << 2) | (((w >> 5) & 1u) << 3); } // extract_data_only (:694)
+                r.changed += c[k].nibble != hard_nib;
+                r.min_margin = std::min(r.min_margin, c[k].margin);
+                e.sum_abs += (double)c[k].sum_abs;
+            }
+            r.codewords += d.n_cw;
+            r.mean_abs_llr = (float)(e.sum_abs / (double)(8u * ppm_h + r.payload_symbols * ppm_p));
+            r.status = LORA_HIP_SOFT_FRAME;
+            lora_hip_frame_info_t info;
+            info.stream = pre[i].stream;
+            info.length = (uint32_t)kLoratapLen + 3u + r.payload_length;
+            info.header_pos = pre[i].header_pos;
+            info.end_pos = pre[i].header_pos + (int64_t)(8u + e.taken) * sps;
+            uint8_t *blob = h->frames.push(info.length, info); // zero-filled loratap header
+            std::memcpy(blob + kLoratapLen, e.phdr, 3);
+            if (r.payload_length) std::memcpy(blob + kLoratapLen + 3, bytes.data() + d.byte_out, r.payload_length);
+            lora_hip_frame_check_t fc;
+            if (lora_hip_check_frame(blob, info.length, &fc) == LORA_HIP_OK) r.crc_ok = fc.crc_ok;
+        }
+        if (reports) reports[i] = r;
+    }
     return LORA_HIP_OK;
 }
 

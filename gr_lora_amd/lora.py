@@ -22,6 +22,9 @@ Same names, argument order and meaning as the reference module `lora`:
                                               the device, in front of any receiver, for captures at 2.4, 2.048, 1.92 ... Msps)
   lora.iq_conditioner(block, window, dc, iq)  (not upstream: removes a direct-conversion front end's DC offset and IQ imbalance on the
                                               device, estimated from block moments; the first stage, in front of the resampler)
+  lora.weak_signal_receiver(samp_rate, bandwidth, sf, cr, crc, reduced_rate, threshold, require_header_checksum, soft)
+                                              (not upstream: the low-SNR receive path on one whole capture - the FFT-domain preamble
+                                              detector, then the soft-decision decoder at its header positions; batch, not streaming)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -819,6 +822,84 @@ class modulator:
 
     def close(self):
         self._tx.close()
+
+
+class weak_signal_receiver(_MsgBlock):
+    """The low-SNR receive path on one whole capture: lora_hip_detect_preambles_device finds the preambles in the dechirped spectrum, where
+    the reference's time-domain gates acquire nothing, and lora_hip_soft_decode_at_headers_device decodes from those header positions with
+    soft decisions (include/lora_hip_soft.h; soft=False: lora_hip_decode_at_headers_device's hard decisions, for comparison).  Explicit
+    header, FFT demodulator, no drift correction.  Frames are published on "frames".
+
+    SF 7 .. 12 (the soft decoder needs the five header codewords an SF6 header block has no room for: ValueError).
+
+    Batch, not streaming: every call of work() is a capture of its own, nothing is carried from one call to the next, and a frame cut by
+    the end of the capture is lost."""
+
+    def __init__(self, samp_rate, bandwidth, sf, cr, crc, reduced_rate=False, threshold=0, require_header_checksum=True, soft=True, device=0):
+        super().__init__()
+        if not 7 <= int(sf) <= 12:
+            raise ValueError("weak_signal_receiver: sf must be 7 .. 12, not %r" % (sf,))
+        self.threshold, self.soft, self.device = float(threshold), bool(soft), int(device)
+        self.flags = capi.SOFT_REQUIRE_HEADER_CHECKSUM if require_header_checksum else 0
+        self._h = capi.Handle(samp_rate=samp_rate, bandwidth=bandwidth, sf=sf, implicit=False, cr=cr, crc=crc, reduced_rate=reduced_rate,
+                              disable_drift_correction=True, device=device, demod=capi.DEMOD_FFT)
+        self.message_port_register_out("frames")
+
+    def _device_cf32(self, capture, scale):
+        """(tensor that owns the complex64 items on the device, their count)"""
+        import torch
+        x = capture
+        dev = torch.device("cuda", self.device)
+        if not (hasattr(x, "is_cuda") and x.is_cuda):
+            raw = _integer_iq(x, scale)
+            x = torch.from_numpy(raw[0]).to(dev) if raw is not None else torch.from_numpy(np.ascontiguousarray(x, dtype=np.complex64).view(np.float32)).to(dev)
+        t = x.contiguous()
+        if t.device.index != self.device:
+            raise ValueError("weak_signal_receiver.work: the tensor is on %s, the receiver on cuda:%d" % (t.device, self.device))
+        fmt = {torch.int16: iqformat.SC16, torch.int8: iqformat.SC8, torch.uint8: iqformat.CU8}.get(t.dtype)
+        if fmt is not None:
+            if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 2)) or t.numel() % 2:
+                raise ValueError("weak_signal_receiver.work: integer IQ must be flat interleaved pairs or shaped (n, 2), not %s" % (tuple(t.shape),))
+            n = t.numel() // 2
+            y = torch.empty(max(n, 1), dtype=torch.complex64, device=dev)
+            capi.unpack_device(t.data_ptr(), n, fmt, y.data_ptr(), iqformat.check_scale(scale), self.device, torch.cuda.current_stream(dev).cuda_stream)
+            return y, n
+        if scale:
+            raise TypeError("weak_signal_receiver.work: scale applies to integer IQ, not to %s" % t.dtype)
+        if t.dtype == torch.complex64:
+            return t, t.numel()
+        if t.dtype == torch.float32 and t.numel() % 2 == 0:
+            return t, t.numel() // 2
+        raise TypeError("weak_signal_receiver.work: a capture is complex64, float32 interleaved or int16 / int8 / uint8 IQ, not %s" % t.dtype)
+
+    def work(self, capture, scale=0) -> List[dict]:
+        """One whole capture: numpy complex64, integer IQ (int16 / int8 / uint8, flat interleaved or (n, 2), with an optional scale), or a
+        torch CUDA tensor of either kind.  -> one dict per detected preamble, in the detector's order: its fields (header_pos, cfo_hz, pmr ...),
+        the decoder's report (soft: status, cr, payload_length, crc_ok, changed, min_margin ...) and "frame": the published blob or None."""
+        import torch
+        t, n = self._device_cf32(capture, scale)
+        stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
+        det = self._h.detect_preambles_device(t.data_ptr(), n, [0], [n], self.threshold, stream)
+        det = [d for d in det if d["header_pos"] + 2 * self._h.sps <= n]   # (a header inside the capture's last two symbols: cut by its end)
+        if self.soft:
+            reports = self._h.soft_decode_at_headers_device(t.data_ptr(), n, [0], [n], det, self.flags, stream)
+        else:
+            self._h.decode_at_headers_device(t.data_ptr(), n, [0], [n], det, stream)
+            reports = [dict() for _ in det]
+        frames = self._h.drain()
+        out, k = [], 0
+        for d, r in zip(det, reports):
+            blob = None
+            if k < len(frames) and frames[k][1].header_pos == d["header_pos"]:
+                blob = frames[k][0]
+                k += 1
+            out.append(dict(d, **r, frame=blob))
+        for blob, _info in frames:
+            self.message_port_pub("frames", blob)
+        return out
+
+    def close(self):
+        self._h.close()
 
 
 class lora_receiver(_MsgBlock):
