@@ -86,10 +86,13 @@ EXPORTS_CONDITIONER = [
     "lora_hip_conditioner_set_fixed", "lora_hip_conditioner_set_adaptive", "lora_hip_conditioner_block_records", "lora_hip_conditioner_last_kernel_ms",
 ]
 
-EXPORTS_SOFT = ["lora_hip_soft_symbols_device", "lora_hip_soft_decode_at_headers_device"]
+EXPORTS_SOFT = ["lora_hip_soft_symbols_device", "lora_hip_soft_decode_at_headers_device", "lora_hip_soft_crc_repair_enable",
+                "lora_hip_soft_crc_repair_results", "lora_hip_soft_crc_repair_codewords"]
 
 SOFT_REQUIRE_HEADER_CHECKSUM = 1   # include/lora_hip_soft.h
 SOFT_FRAME, SOFT_HEADER_REJECTED, SOFT_CR_ZERO, SOFT_TRUNCATED = 0, 1, 2, 3   # lora_hip_soft_report_t.status
+SOFT_REPAIR_NOT_ATTEMPTED, SOFT_REPAIR_CRC_HELD, SOFT_REPAIR_REPAIRED, SOFT_REPAIR_FAILED = 0, 1, 2, 3   # lora_hip_soft_repair_t.status
+SOFT_REPAIR_MAX_CANDIDATES = 8
 FILTERBANK_MAX_DST = 8        # include/lora_hip_filterbank.h
 CONDITIONER_FLAG_DC, CONDITIONER_FLAG_IQ = 1, 2   # include/lora_hip_conditioner.h
 SPECTRUM_WINDOW_HANN, SPECTRUM_WINDOW_RECT = 0, 1   # include/lora_hip_spectrum.h
@@ -178,6 +181,16 @@ class SoftReport(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _t in self._fields_ if k != "reserved"}
+
+
+class SoftRepair(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("candidates", C.c_uint32), ("pattern", C.c_uint32), ("changed", C.c_uint32), ("syndrome", C.c_uint16),
+                ("reserved", C.c_uint16), ("penalty", C.c_float), ("codeword", C.c_uint16 * 8)]
+
+    def as_dict(self) -> dict:
+        """the keys of softdecode.crc_repair's record; codewords: the candidates' body codeword indices, candidate 0 first"""
+        return dict(status=self.status, candidates=self.candidates, pattern=self.pattern, changed=self.changed, syndrome=self.syndrome,
+                    penalty=np.float32(self.penalty), codewords=list(self.codeword[: self.candidates]))
 
 
 class GatewayConfig(C.Structure):
@@ -475,6 +488,10 @@ def load():
         L.lora_hip_soft_symbols_device.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp]
         L.lora_hip_soft_decode_at_headers_device.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.POINTER(Preamble), C.c_size_t, C.c_uint32,
                                                              C.POINTER(SoftReport), vp]
+    if hasattr(L, "lora_hip_soft_crc_repair_enable") or not os.environ.get("LORA_HIP_LIB"):   # (as above)
+        L.lora_hip_soft_crc_repair_enable.argtypes = [vp, C.c_uint32]
+        L.lora_hip_soft_crc_repair_results.argtypes = [vp, C.POINTER(SoftRepair), C.c_size_t]
+        L.lora_hip_soft_crc_repair_codewords.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, C.POINTER(SoftRepair), vp]
     _lib = L
     return L
 
@@ -695,7 +712,40 @@ class Handle:
         rep = (SoftReport * max(len(preambles), 1))()
         self._check(self.L.lora_hip_soft_decode_at_headers_device(self.h, dev_ptr, total_items, o.ctypes.data, l.ctypes.data, o.size, arr, len(preambles), int(flags),
                                                                   rep, stream))
+        self._soft_entries = len(preambles)
         return [r.as_dict() for r in rep[: len(preambles)]]
+
+    def soft_crc_repair_enable(self, candidates: int):
+        """lora_hip_soft_crc_repair_enable: 0 off (the default), 1 .. 8: CRC-aided repair with that many candidates in later soft_decode_at_headers_device calls"""
+        if not 0 <= int(candidates) <= SOFT_REPAIR_MAX_CANDIDATES:
+            raise ValueError("crc repair candidates: 0 .. %d, not %r" % (SOFT_REPAIR_MAX_CANDIDATES, candidates))
+        self._check(self.L.lora_hip_soft_crc_repair_enable(self.h, int(candidates)))
+
+    def soft_crc_repair_results(self) -> List[dict]:
+        """lora_hip_soft_crc_repair_results: the repair records of the last soft_decode_at_headers_device call, one dict per entry"""
+        n = getattr(self, "_soft_entries", 0)
+        rec = (SoftRepair * max(n, 1))()
+        self._check(self.L.lora_hip_soft_crc_repair_results(self.h, rec, n))
+        return [r.as_dict() for r in rec[:n]]
+
+    def soft_crc_repair_codewords(self, lengths: Sequence[int], nibbles, seconds, margins, candidates: int, stream: int = 0):
+        """lora_hip_soft_crc_repair_codewords: the repair kernel alone.  lengths[f]: payload bytes in front of the CRC bytes; nibbles / seconds /
+        margins: the 2 * (lengths[f] + 2) body codewords of every frame, back to back -> (list of repaired bodies, list of record dicts)"""
+        ln = np.ascontiguousarray(lengths, dtype=np.uint32)
+        nib, sec = np.ascontiguousarray(nibbles, dtype=np.uint8), np.ascontiguousarray(seconds, dtype=np.uint8)
+        mar = np.ascontiguousarray(margins, dtype=np.float32)
+        n_cw = int(2 * (ln.astype(np.int64) + 2).sum())
+        if not (nib.size == sec.size == mar.size == n_cw):
+            raise ValueError("2 * (length + 2) codewords per frame: %d expected" % n_cw)
+        out = np.zeros(max(n_cw // 2, 1), dtype=np.uint8)
+        rec = (SoftRepair * max(ln.size, 1))()
+        self._check(self.L.lora_hip_soft_crc_repair_codewords(self.h, ln.size, ln.ctypes.data, nib.ctypes.data, sec.ctypes.data, mar.ctypes.data, int(candidates),
+                                                              out.ctypes.data, rec, stream))
+        bodies, at = [], 0
+        for v in ln:
+            bodies.append(bytes(out[at:at + int(v) + 2]))
+            at += int(v) + 2
+        return bodies, [r.as_dict() for r in rec[: ln.size]]
 
     def frames_available(self) -> int:
         return self.L.lora_hip_frames_available(self.h)

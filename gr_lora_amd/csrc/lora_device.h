@@ -280,10 +280,22 @@ struct SoftFrameDesc { // one frame in one launch of soft_chain_kernel (host-wri
     uint32_t byte_out; // its first assembled byte
     uint32_t n_bytes;  // bytes to assemble, low nibble first (0 in the header launch: the host builds the three header bytes)
 };
-struct SoftCw { float margin, sum_abs; uint8_t nibble, hard, pad[2]; }; // (device-written) hard: the de-whitened word of the LLR signs
+struct SoftCw { float margin, sum_abs; uint8_t nibble, hard, second, pad; }; // (device-written) hard: the de-whitened word of the LLR signs; second: the runner-up nibble
+constexpr uint32_t kSoftRepairMaxCand = 8;   // one pattern per lane of a 256-thread workgroup
+constexpr uint32_t kSoftRepairMaxBody = 257; // bytes of a frame body: length <= 255 and the two CRC bytes
+struct SoftRepairDesc { // one frame with a payload CRC in one launch of soft_repair_kernel (host-written)
+    uint32_t cw_in;    // its first body codeword record (spare header codewords first)
+    uint32_t n_cw;     // records there
+    uint32_t byte_io;  // its first assembled byte
+    uint32_t length;   // payload bytes in front of the two CRC bytes (<= 255)
+    uint32_t whiten;   // whitening of the two CRC bytes: w[length] | w[length + 1] << 8
+};
+struct SoftRepairRec { uint32_t status, candidates, pattern, changed; uint16_t syndrome, reserved; float penalty; uint16_t codeword[kSoftRepairMaxCand]; }; // lora_hip_soft_repair_t
 int launch_soft_symbols(const DevParams &p, const float2 *iq, const int64_t *d_offsets, const uint8_t *d_reduced, uint32_t n, float *d_llr, SoftSym *d_sym, void *stream);
 // frames on grid x, 64 pairs of codewords per workgroup on grid y (max_pairs: the largest max(ceil(n_cw / 2), n_bytes) of the launch)
 int launch_soft_chain(const DevParams &p, const SoftFrameDesc *d_descs, uint32_t n_frames, uint32_t max_pairs, const float *d_llr_hdr, const float *d_llr_pay, SoftCw *d_cws,
                       uint8_t *d_bytes, void *stream);
+// one workgroup per frame: CRC-aided repair of d_bytes from the codeword records (candidates: 1 .. kSoftRepairMaxCand)
+int launch_soft_repair(const SoftRepairDesc *d_descs, uint32_t n_frames, uint32_t candidates, const SoftCw *d_cws, uint8_t *d_bytes, SoftRepairRec *d_recs, void *stream);
 
 } // namespace lora_hip

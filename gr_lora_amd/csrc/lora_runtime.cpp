@@ -245,7 +245,16 @@ struct lora_hip_decoder {
         DevBuf<SoftSym> d_sym;
         DevBuf<SoftFrameDesc> d_descs;
         DevBuf<SoftCw> d_cws;
-        void release() { d_llr_hdr.release(); d_llr_pay.release(); d_reduced.release(); d_bytes.release(); d_sym.release(); d_descs.release(); d_cws.release(); }
+        // CRC-aided repair: 0 = off; the records of the last decode call, one per entry
+        uint32_t repair_candidates = 0;
+        DevBuf<SoftRepairDesc> d_rdescs;
+        DevBuf<SoftRepairRec> d_rrecs;
+        std::vector<lora_hip_soft_repair_t> repair_results;
+        void release()
+        {
+            d_llr_hdr.release(); d_llr_pay.release(); d_reduced.release(); d_bytes.release(); d_sym.release(); d_descs.release(); d_cws.release();
+            d_rdescs.release(); d_rrecs.release();
+        }
     } soft;
     struct PayState { std::vector<uint32_t> active; size_t used = 0, cap_sym = 0, n_sym = 0; int round = 0; float ms = 0.0f; bool open = false; } pay;
 };
@@ -2427,8 +2436,9 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
     if (h->pass_open) return fail(h, LORA_HIP_ERR_ARG, "lora_hip_soft_decode_at_headers_device: a pass is open on this handle");
     if (h->P.implicit) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "decode at given headers needs an explicit header");
     if (h->P.sf < 7u) return fail(h, LORA_HIP_ERR_BAD_CONFIG, "soft decoding needs sf >= 7: the header block of an explicit header holds 5 codewords, sf - 2 = %u fit", h->P.sf - 2u);
-    if (n == 0) return LORA_HIP_OK;
     if (n > 0x7fffffffu / (8u * kSoftStride)) return fail(h, LORA_HIP_ERR_ARG, "too many entries for one call");
+    h->soft.repair_results.assign(n, lora_hip_soft_repair_t{}); // NOT_ATTEMPTED
+    if (n == 0) return LORA_HIP_OK;
     const int64_t sps = h->P.sps;
     const uint32_t sf = h->P.sf, ppm_h = sf - 2u, ppm_p = h->P.reduced_rate ? sf - 2u : sf, n_spare = sf - 7u;
     for (size_t i = 0; i < n; i++) {
@@ -2445,7 +2455,7 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
         hamming84_decode_table(t);
         return std::vector<uint8_t>(t, t + 256);
     }();
-    struct Ent { lora_hip_soft_report_t rep; uint8_t phdr[3]; bool have_hdr, go; uint32_t slot, taken, desc; double sum_abs; };
+    struct Ent { lora_hip_soft_report_t rep; uint8_t phdr[3]; bool have_hdr, go; uint32_t slot, taken, desc, rdesc; double sum_abs; };
     std::vector<Ent> ent(n, Ent{});
     // stage 1: the eight header windows of every entry, one launch; their five header codewords, one more; the host reads the headers
     std::vector<int64_t> offs;
@@ -2459,6 +2469,9 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
         for (int k = 0; k < 8; k++) { offs.push_back((int64_t)stream_off[s] + pre[i].header_pos + k * sps); red.push_back(1); }
     }
     std::vector<SoftFrameDesc> descs;
+    std::vector<SoftRepairDesc> rdescs; // where repair is on: the frames with a payload CRC
+    std::vector<SoftRepairRec> rrecs;
+    const uint32_t repair = h->soft.repair_candidates;
     std::vector<SoftCw> cws;
     HIP_TRY(h, h->soft.d_bytes.reserve(16));
     HIP_TRY(h, h->soft.d_llr_pay.reserve(16));
@@ -2504,6 +2517,12 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
         e.go = true; e.desc = (uint32_t)descs.size();
         SoftFrameDesc d{e.slot * 8u, (uint32_t)offs.size(), 5u, n_spare, n_spare + (n_sym / (uint32_t)spb) * ppm_p, (uint32_t)spb, ppm_p, r.cr <= 2u ? 1u : 2u, n_cw_all, n_bytes_all, r.payload_length};
         for (uint32_t k = 0; k < n_sym; k++) { offs.push_back((int64_t)stream_off[s] + pre[i].header_pos + (int64_t)(8u + k) * sps); red.push_back((uint8_t)(h->P.reduced_rate ? 1 : 0)); }
+        e.rdesc = 0xffffffffu;
+        if (repair && r.has_crc) {
+            const uint32_t length = e.phdr[0];
+            e.rdesc = (uint32_t)rdescs.size();
+            rdescs.push_back(SoftRepairDesc{d.cw_out, d.n_cw, d.byte_out, length, (uint32_t)lora_frame::whiten_at(length) | ((uint32_t)lora_frame::whiten_at(length + 1u) << 8)});
+        }
         n_cw_all += d.n_cw; n_bytes_all += d.n_bytes;
         max_pairs = std::max(max_pairs, std::max((d.n_cw + 1u) / 2u, d.n_bytes));
         descs.push_back(d);
@@ -2521,6 +2540,15 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
         HIP_TRY(h, hipMemcpyAsync(h->soft.d_descs.p, descs.data(), descs.size() * sizeof(SoftFrameDesc), hipMemcpyHostToDevice, st));
         if (launch_soft_chain(h->P, h->soft.d_descs.p, (uint32_t)descs.size(), max_pairs, h->soft.d_llr_hdr.p, h->soft.d_llr_pay.p, h->soft.d_cws.p, h->soft.d_bytes.p, st) != 0)
             return fail(h, LORA_HIP_ERR_HIP, "soft chain launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (!rdescs.empty()) { // behind the chain and in front of the copies back: the bytes copied are the repaired ones
+            rrecs.resize(rdescs.size());
+            HIP_TRY(h, h->soft.d_rdescs.reserve(rdescs.size()));
+            HIP_TRY(h, h->soft.d_rrecs.reserve(rdescs.size()));
+            HIP_TRY(h, hipMemcpyAsync(h->soft.d_rdescs.p, rdescs.data(), rdescs.size() * sizeof(SoftRepairDesc), hipMemcpyHostToDevice, st));
+            if (launch_soft_repair(h->soft.d_rdescs.p, (uint32_t)rdescs.size(), repair, h->soft.d_cws.p, h->soft.d_bytes.p, h->soft.d_rrecs.p, st) != 0)
+                return fail(h, LORA_HIP_ERR_HIP, "soft repair launch failed: %s", hipGetErrorString(hipGetLastError()));
+            HIP_TRY(h, hipMemcpyAsync(rrecs.data(), h->soft.d_rrecs.p, rrecs.size() * sizeof(SoftRepairRec), hipMemcpyDeviceToHost, st));
+        }
         if (n_cw_all) HIP_TRY(h, hipMemcpyAsync(cws.data(), h->soft.d_cws.p, cws.size() * sizeof(SoftCw), hipMemcpyDeviceToHost, st));
         if (n_bytes_all) HIP_TRY(h, hipMemcpyAsync(bytes.data(), h->soft.d_bytes.p, bytes.size(), hipMemcpyDeviceToHost, st));
         HIP_TRY(h, hipStreamSynchronize(st));
@@ -2552,10 +2580,69 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
             if (r.payload_length) std::memcpy(blob + kLoratapLen + 3, bytes.data() + d.byte_out, r.payload_length);
             lora_hip_frame_check_t fc;
             if (lora_hip_check_frame(blob, info.length, &fc) == LORA_HIP_OK) r.crc_ok = fc.crc_ok;
+            if (e.rdesc != 0xffffffffu) std::memcpy(&h->soft.repair_results[i], &rrecs[e.rdesc], sizeof(lora_hip_soft_repair_t));
         }
         if (reports) reports[i] = r;
     }
     return LORA_HIP_OK;
 }
+
+lora_hip_status lora_hip_soft_crc_repair_enable(lora_hip_decoder_t *h, uint32_t candidates)
+{
+    if (!h || candidates > LORA_HIP_SOFT_REPAIR_MAX_CANDIDATES) return LORA_HIP_ERR_ARG;
+    h->soft.repair_candidates = candidates;
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_soft_crc_repair_results(lora_hip_decoder_t *h, lora_hip_soft_repair_t *out, size_t n)
+{
+    if (!h || (n && !out) || n != h->soft.repair_results.size()) return LORA_HIP_ERR_ARG;
+    std::copy(h->soft.repair_results.begin(), h->soft.repair_results.end(), out);
+    return LORA_HIP_OK;
+}
+
+lora_hip_status lora_hip_soft_crc_repair_codewords(lora_hip_decoder_t *h, size_t n_frames, const uint32_t *length, const uint8_t *nibble,
+                                                   const uint8_t *second, const float *margin, uint32_t candidates, uint8_t *bytes_out,
+                                                   lora_hip_soft_repair_t *records_out, void *hip_stream)
+{
+    if (!h || candidates < 1u || candidates > LORA_HIP_SOFT_REPAIR_MAX_CANDIDATES || n_frames > 0x7fffffffu / (2u * kSoftRepairMaxBody)) return LORA_HIP_ERR_ARG;
+    if (n_frames && (!length || !nibble || !second || !margin || !bytes_out || !records_out)) return LORA_HIP_ERR_ARG;
+    std::vector<SoftRepairDesc> rdescs;
+    uint32_t n_bytes = 0;
+    for (size_t f = 0; f < n_frames; f++) {
+        if (length[f] > 255u) return fail(h, LORA_HIP_ERR_ARG, "frame %zu: length %u", f, length[f]);
+        const uint32_t body = length[f] + 2u;
+        rdescs.push_back(SoftRepairDesc{2u * n_bytes, 2u * body, n_bytes, length[f], (uint32_t)lora_frame::whiten_at(length[f]) | ((uint32_t)lora_frame::whiten_at(length[f] + 1u) << 8)});
+        n_bytes += body;
+    }
+    std::vector<SoftCw> cws(2u * (size_t)n_bytes, SoftCw{});
+    std::vector<uint8_t> bytes(n_bytes);
+    for (size_t c = 0; c < cws.size(); c++) {
+        if (nibble[c] > 15u || second[c] > 15u) return fail(h, LORA_HIP_ERR_ARG, "codeword %zu: a nibble above 15", c);
+        cws[c].margin = margin[c]; cws[c].nibble = nibble[c]; cws[c].second = second[c];
+        bytes[c >> 1] = (uint8_t)(bytes[c >> 1] | (nibble[c] << (4u * (c & 1u))));
+    }
+    if (n_frames == 0) return LORA_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<SoftRepairRec> rrecs(n_frames);
+    HIP_TRY(h, h->soft.d_rdescs.reserve(n_frames));
+    HIP_TRY(h, h->soft.d_rrecs.reserve(n_frames));
+    HIP_TRY(h, h->soft.d_cws.reserve(cws.size()));
+    HIP_TRY(h, h->soft.d_bytes.reserve(bytes.size()));
+    HIP_TRY(h, hipMemcpyAsync(h->soft.d_rdescs.p, rdescs.data(), rdescs.size() * sizeof(SoftRepairDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->soft.d_cws.p, cws.data(), cws.size() * sizeof(SoftCw), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(h->soft.d_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, st));
+    if (launch_soft_repair(h->soft.d_rdescs.p, (uint32_t)n_frames, candidates, h->soft.d_cws.p, h->soft.d_bytes.p, h->soft.d_rrecs.p, st) != 0)
+        return fail(h, LORA_HIP_ERR_HIP, "soft repair launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(h, hipMemcpyAsync(bytes.data(), h->soft.d_bytes.p, bytes.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(rrecs.data(), h->soft.d_rrecs.p, rrecs.size() * sizeof(SoftRepairRec), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::copy(bytes.begin(), bytes.end(), bytes_out);
+    std::memcpy(records_out, rrecs.data(), rrecs.size() * sizeof(SoftRepairRec));
+    return LORA_HIP_OK;
+}
+
+static_assert(sizeof(SoftRepairRec) == sizeof(lora_hip_soft_repair_t) && sizeof(lora_hip_soft_repair_t) == 40, "the device's repair record is lora_hip_soft_repair_t");
 
 } // extern "C"

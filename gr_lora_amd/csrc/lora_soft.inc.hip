@@ -211,18 +211,18 @@ __device__ __forceinline__ SoftCw soft_codeword(const DevParams &P, const SoftFr
         Dv[j] = wbit ? -Cs[j] : Cs[j];
     }
     float best = -INFINITY, second = -INFINITY;
-    uint32_t nib = 0;
+    uint32_t nib = 0, nib2 = 0;
 #pragma unroll
     for (uint32_t s = 0; s < 16u; s++) {
         const uint32_t e = hamming84_encode(s);
         float sc = 0.0f;
 #pragma unroll
         for (uint32_t j = 0; j < 8u; j++) sc += ((e >> j) & 1u) ? -Dv[j] : Dv[j];
-        if (sc > best) { second = best; best = sc; nib = s; }
-        else if (sc > second) second = sc;
+        if (sc > best) { second = best; nib2 = nib; best = sc; nib = s; } // (a displaced best has the smaller index: the first of equal runners-up stays)
+        else if (sc > second) { second = sc; nib2 = s; }
     }
     SoftCw o;
-    o.margin = best - second; o.sum_abs = sa; o.nibble = (uint8_t)nib; o.hard = (uint8_t)hard; o.pad[0] = 0; o.pad[1] = 0;
+    o.margin = best - second; o.sum_abs = sa; o.nibble = (uint8_t)nib; o.hard = (uint8_t)hard; o.second = (uint8_t)nib2; o.pad = 0;
     return o;
 }
 
@@ -249,5 +249,139 @@ int launch_soft_chain(const DevParams &p, const SoftFrameDesc *d_descs, uint32_t
     if (n_frames == 0 || max_pairs == 0) return 0;
     if (ensure_constants() != 0) return -1;
     hipLaunchKernelGGL(soft_chain_kernel, dim3(n_frames, (max_pairs + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p, d_descs, d_llr_hdr, d_llr_pay, d_cws, d_bytes);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- CRC-aided repair of the least reliable codewords (softdecode.crc_repair) ------------------------------------------
+// The payload CRC (lora_frame_check.h: CCITT from 0 over all but the last two payload bytes, those XORed in, no final XOR) XOR the received,
+// de-whitened CRC bytes is affine over GF(2) in the bits of the frame body: the syndrome is the XOR of one 16-bit word per body byte and of the
+// whitening constant, and giving a codeword its runner-up nibble changes it by one fixed word.  All of it is integer arithmetic but the penalty.
+
+// a * b in GF(2)[x] mod x^16 + x^12 + x^5 + 1; a, b < 2^16
+__device__ __forceinline__ uint32_t soft_gf_mul(uint32_t a, uint32_t b)
+{
+    uint32_t r = 0;
+    for (int i = 15; i >= 0; i--) {
+        r = (r << 1) ^ ((r & 0x8000u) ? 0x11021u : 0u);
+        if ((b >> i) & 1u) r ^= a;
+    }
+    return r;
+}
+
+// what the value v at byte k of a body of length + 2 bytes adds to the syndrome: the received CRC bytes low byte first; payload byte k with
+// m = length - 1 - k bytes behind it: m = 0 enters as the low byte, m = 1 as the high byte, m >= 2 is the high byte advanced 8 (m - 1) steps
+__device__ __forceinline__ uint32_t soft_syn_of_byte(uint32_t v, uint32_t k, uint32_t length)
+{
+    if (k >= length) return k == length ? v : v << 8;
+    uint32_t m = length - 1u - k;
+    if (m == 0u) return v;
+    uint32_t r = 1u, p = 0x100u; // x^(8 (m - 1)) by squaring
+    for (m -= 1u; m; m >>= 1) {
+        if (m & 1u) r = soft_gf_mul(r, p);
+        p = soft_gf_mul(p, p);
+    }
+    return soft_gf_mul(v << 8, r);
+}
+
+// One 256-thread workgroup per frame.  Syndrome: a byte per lane (two for lanes 0 of the longest bodies), XOR over the wavefront by shuffles and
+// over the four wavefronts through LDS.  Candidates: the rank of every eligible codeword under (margin, c), counted against the margins in LDS
+// (reads of one address by all lanes: a broadcast) - ranks below n_cand name the candidates.  Patterns: lane p owns pattern p.
+__global__ __launch_bounds__(kWG) void soft_repair_kernel(const SoftRepairDesc *descs, uint32_t n_frames, uint32_t max_cand, const SoftCw *cws, uint8_t *bytes, SoftRepairRec *recs)
+{
+#pragma clang fp contract(off)
+    __shared__ float s_margin[2u * kSoftRepairMaxBody];
+    __shared__ uint32_t s_syn[kWG / 64], s_pat[kWG / 64], s_cand[kSoftRepairMaxCand], s_e[kSoftRepairMaxCand];
+    __shared__ float s_pen[kWG / 64], s_m[kSoftRepairMaxCand];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
+        const SoftRepairDesc d = descs[f];
+        const uint32_t n_body = d.length + 2u;
+        const uint32_t n_elig = 2u * n_body < d.n_cw ? 2u * n_body : d.n_cw;
+        const uint32_t n_cand = max_cand < n_elig ? max_cand : n_elig;
+        uint32_t syn = 0;
+        for (uint32_t k = tid; k < n_body; k += kWG) syn ^= soft_syn_of_byte(bytes[d.byte_io + k], k, d.length);
+        for (uint32_t c = tid; c < n_elig; c += kWG) s_margin[c] = cws[d.cw_in + c].margin;
+        if (tid < kSoftRepairMaxCand) s_cand[tid] = 0u;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) syn ^= (uint32_t)__shfl_xor((int)syn, o, 64);
+        if (lane == 0u) s_syn[wave] = syn;
+        __syncthreads();
+        syn = (s_syn[0] ^ s_syn[1] ^ s_syn[2] ^ s_syn[3] ^ d.whiten) & 0xffffu;
+        if (syn == 0u) { // (the same in every lane)
+            if (tid == 0u) {
+                SoftRepairRec r = {};
+                r.status = 1u; // CRC_HELD
+                recs[f] = r;
+            }
+        } else {
+            for (uint32_t c = tid; c < n_elig; c += kWG) {
+                const float m = s_margin[c];
+                uint32_t rank = 0;
+                for (uint32_t o = 0; o < n_elig; o++) {
+                    const float mo = s_margin[o];
+                    rank += (mo < m || (mo == m && o < c)) ? 1u : 0u;
+                }
+                if (rank < n_cand) s_cand[rank] = c;
+            }
+            __syncthreads();
+            if (tid < kSoftRepairMaxCand) {
+                uint32_t e = 0;
+                float m = 0.0f;
+                if (tid < n_cand) {
+                    const uint32_t c = s_cand[tid];
+                    const SoftCw w = cws[d.cw_in + c];
+                    e = soft_syn_of_byte((uint32_t)((w.nibble ^ w.second) & 15u) << (4u * (c & 1u)), c >> 1, d.length);
+                    m = s_margin[c];
+                }
+                s_e[tid] = e; s_m[tid] = m;
+            }
+            __syncthreads();
+            float pen = INFINITY;
+            uint32_t pat = 0xffffffffu; // no match
+            if (tid >= 1u && tid < (1u << n_cand)) {
+                uint32_t x = 0;
+                float s = 0.0f;
+                for (uint32_t i = 0; i < n_cand; i++)
+                    if ((tid >> i) & 1u) { x ^= s_e[i]; s += s_m[i]; }
+                if (x == syn) { pen = s; pat = tid; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float op = __shfl_xor(pen, o, 64);
+                const uint32_t oq = (uint32_t)__shfl_xor((int)pat, o, 64);
+                if (op < pen || (op == pen && oq < pat)) { pen = op; pat = oq; }
+            }
+            if (lane == 0u) { s_pen[wave] = pen; s_pat[wave] = pat; }
+            __syncthreads();
+            if (tid == 0u) {
+                for (uint32_t w = 1; w < kWG / 64; w++)
+                    if (s_pen[w] < pen || (s_pen[w] == pen && s_pat[w] < pat)) { pen = s_pen[w]; pat = s_pat[w]; }
+                SoftRepairRec r = {};
+                r.status = 3u; // FAILED
+                r.candidates = n_cand; r.syndrome = (uint16_t)syn;
+                for (uint32_t i = 0; i < n_cand; i++) r.codeword[i] = (uint16_t)s_cand[i];
+                if (pat != 0xffffffffu) {
+                    r.status = 2u; // REPAIRED
+                    r.pattern = pat; r.changed = (uint32_t)__popc(pat); r.penalty = pen;
+                    for (uint32_t i = 0; i < n_cand; i++) // one lane, one byte after the other: two candidates may share a byte
+                        if ((pat >> i) & 1u) {
+                            const uint32_t c = s_cand[i];
+                            const SoftCw w = cws[d.cw_in + c];
+                            uint8_t *b = bytes + d.byte_io + (c >> 1);
+                            *b = (uint8_t)(*b ^ (((w.nibble ^ w.second) & 15u) << (4u * (c & 1u))));
+                        }
+                }
+                recs[f] = r;
+            }
+        }
+        __syncthreads(); // the LDS is reused by the next frame of this workgroup
+    }
+}
+
+int launch_soft_repair(const SoftRepairDesc *d_descs, uint32_t n_frames, uint32_t candidates, const SoftCw *d_cws, uint8_t *d_bytes, SoftRepairRec *d_recs, void *stream)
+{
+    if (n_frames == 0) return 0;
+    if (candidates < 1u || candidates > kSoftRepairMaxCand) return -1;
+    hipLaunchKernelGGL(soft_repair_kernel, dim3(n_frames < 4096u ? n_frames : 4096u), dim3(kWG), 0, (hipStream_t)stream, d_descs, n_frames, candidates, d_cws, d_bytes, d_recs);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -22,9 +22,11 @@ Same names, argument order and meaning as the reference module `lora`:
                                               the device, in front of any receiver, for captures at 2.4, 2.048, 1.92 ... Msps)
   lora.iq_conditioner(block, window, dc, iq)  (not upstream: removes a direct-conversion front end's DC offset and IQ imbalance on the
                                               device, estimated from block moments; the first stage, in front of the resampler)
-  lora.weak_signal_receiver(samp_rate, bandwidth, sf, cr, crc, reduced_rate, threshold, require_header_checksum, soft)
+  lora.weak_signal_receiver(samp_rate, bandwidth, sf, cr, crc, reduced_rate, threshold, require_header_checksum, soft, crc_repair=0)
                                               (not upstream: the low-SNR receive path on one whole capture - the FFT-domain preamble
-                                              detector, then the soft-decision decoder at its header positions; batch, not streaming)
+                                              detector, then the soft-decision decoder at its header positions; batch, not streaming.
+                                              crc_repair = 1 .. 8: a frame whose payload CRC fails is repaired on the device by giving
+                                              up to that many of its least reliable codewords their runner-up nibble; off by default)
   lora.message_socket_sink(ip, port, layer)   (lib/message_socket_sink_impl.cc:93-122)
   lora.message_file_sink(path)                (lib/message_file_sink_impl.cc)
 Blocks exchange frames through message ports named as upstream ("frames",
@@ -832,17 +834,27 @@ class weak_signal_receiver(_MsgBlock):
 
     SF 7 .. 12 (the soft decoder needs the five header codewords an SF6 header block has no room for: ValueError).
 
+    crc_repair = L in 1 .. 8 (soft only; 0, the default: off): lora_hip_soft_crc_repair_enable.  A published frame whose payload CRC fails takes the
+    cheapest pattern of runner-up nibbles among its L least reliable body codewords that makes the CRC hold; every result then carries
+    "repair", the record of what was changed.  A 16-bit CRC also accepts wrong patterns (DESIGN.md 4.19.1 has the measured rate): a frame with
+    repair["status"] == capi.SOFT_REPAIR_REPAIRED is less certain than one whose CRC held.
+
     Batch, not streaming: every call of work() is a capture of its own, nothing is carried from one call to the next, and a frame cut by
     the end of the capture is lost."""
 
-    def __init__(self, samp_rate, bandwidth, sf, cr, crc, reduced_rate=False, threshold=0, require_header_checksum=True, soft=True, device=0):
+    def __init__(self, samp_rate, bandwidth, sf, cr, crc, reduced_rate=False, threshold=0, require_header_checksum=True, soft=True, device=0, crc_repair=0):
         super().__init__()
         if not 7 <= int(sf) <= 12:
             raise ValueError("weak_signal_receiver: sf must be 7 .. 12, not %r" % (sf,))
+        if not 0 <= int(crc_repair) <= capi.SOFT_REPAIR_MAX_CANDIDATES or (crc_repair and not soft):
+            raise ValueError("weak_signal_receiver: crc_repair is 0 .. %d and needs soft=True, not %r" % (capi.SOFT_REPAIR_MAX_CANDIDATES, crc_repair))
+        self.crc_repair = int(crc_repair)
         self.threshold, self.soft, self.device = float(threshold), bool(soft), int(device)
         self.flags = capi.SOFT_REQUIRE_HEADER_CHECKSUM if require_header_checksum else 0
         self._h = capi.Handle(samp_rate=samp_rate, bandwidth=bandwidth, sf=sf, implicit=False, cr=cr, crc=crc, reduced_rate=reduced_rate,
                               disable_drift_correction=True, device=device, demod=capi.DEMOD_FFT)
+        if self.crc_repair:
+            self._h.soft_crc_repair_enable(self.crc_repair)
         self.message_port_register_out("frames")
 
     def _device_cf32(self, capture, scale):
@@ -875,7 +887,8 @@ class weak_signal_receiver(_MsgBlock):
     def work(self, capture, scale=0) -> List[dict]:
         """One whole capture: numpy complex64, integer IQ (int16 / int8 / uint8, flat interleaved or (n, 2), with an optional scale), or a
         torch CUDA tensor of either kind.  -> one dict per detected preamble, in the detector's order: its fields (header_pos, cfo_hz, pmr ...),
-        the decoder's report (soft: status, cr, payload_length, crc_ok, changed, min_margin ...) and "frame": the published blob or None."""
+        the decoder's report (soft: status, cr, payload_length, crc_ok, changed, min_margin ...; with crc_repair also "repair": status,
+        candidates, pattern, changed, syndrome, penalty, codewords) and "frame": the published blob or None."""
         import torch
         t, n = self._device_cf32(capture, scale)
         stream = torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream
@@ -883,6 +896,8 @@ class weak_signal_receiver(_MsgBlock):
         det = [d for d in det if d["header_pos"] + 2 * self._h.sps <= n]   # (a header inside the capture's last two symbols: cut by its end)
         if self.soft:
             reports = self._h.soft_decode_at_headers_device(t.data_ptr(), n, [0], [n], det, self.flags, stream)
+            if self.crc_repair:
+                reports = [dict(r, repair=rec) for r, rec in zip(reports, self._h.soft_crc_repair_results())]
         else:
             self._h.decode_at_headers_device(t.data_ptr(), n, [0], [n], det, stream)
             reports = [dict() for _ in det]

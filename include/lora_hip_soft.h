@@ -74,6 +74,52 @@ lora_hip_status lora_hip_soft_decode_at_headers_device(lora_hip_decoder_t *h, co
                                                        const uint64_t *stream_len, uint32_t n_streams, const lora_hip_preamble_t *pre, size_t n,
                                                        uint32_t flags, lora_hip_soft_report_t *reports, void *hip_stream);
 
+/* ---- CRC-aided repair (off by default; definition: gr_lora_amd/softdecode.py crc_repair) ----
+ * Where a frame is published with a payload CRC that fails, the L least reliable codewords of its body may take their second-best nibble
+ * (the smallest s != nibble with the largest score among the rest: what margin is measured against).
+ *   eligible    the codewords that feed the frame body - spare header codewords first, then payload codewords - at indices
+ *               c < 2 * payload_length.  The five header codewords are never touched
+ *   candidates  the n_cand = min(L, eligible) of them with the smallest (margin, c), margins compared as values; candidate 0 is the least reliable
+ *   syndrome    lora_hip_check_frame's crc_calc ^ crc_rx of the body; affine over GF(2) in the body bits, so candidate i taking its second
+ *               nibble changes it by a fixed 16-bit e[i]
+ *   pattern p   1 .. 2^n_cand - 1 matches iff the XOR of e[i] over its set bits equals the syndrome; penalty = the sum of margin[i] over the
+ *               set bits, i ascending, fp32.  The matching pattern with the smallest (penalty, p) is applied to the published bytes
+ * The 16-bit CRC also accepts wrong patterns: more than 2^L / 65536 of the time, because its last two payload bytes and the CRC bytes enter
+ * by plain XOR and one wrong symbol puts the same bit error into several codewords of a block.  DESIGN.md 4.19.1 has the measured rate.     */
+#define LORA_HIP_SOFT_REPAIR_NOT_ATTEMPTED 0u /* no frame published, or the frame has no CRC, or repair is off */
+#define LORA_HIP_SOFT_REPAIR_CRC_HELD 1u      /* the CRC held: nothing to do, no other field is filled in      */
+#define LORA_HIP_SOFT_REPAIR_REPAIRED 2u      /* a pattern matched and was applied                             */
+#define LORA_HIP_SOFT_REPAIR_FAILED 3u        /* no pattern matched: every byte is as the decoder left it      */
+#define LORA_HIP_SOFT_REPAIR_MAX_CANDIDATES 8u
+
+typedef struct lora_hip_soft_repair {
+    uint32_t status;      /* LORA_HIP_SOFT_REPAIR_NOT_ATTEMPTED ...                                   */
+    uint32_t candidates;  /* n_cand                                                                   */
+    uint32_t pattern;     /* bit i: candidate i took its second nibble; 0 unless REPAIRED             */
+    uint32_t changed;     /* set bits of pattern                                                      */
+    uint16_t syndrome;    /* the value before repair                                                  */
+    uint16_t reserved;
+    float    penalty;     /* of the pattern applied (fp32, the device's own); 0 unless REPAIRED       */
+    uint16_t codeword[8]; /* the body codeword index c of each candidate, 0 past n_cand               */
+} lora_hip_soft_repair_t;
+
+/* candidates: 0 turns repair off (the default), 1 .. 8 turns it on with that L for later lora_hip_soft_decode_at_headers_device calls on this
+ * handle; anything else: ERR_ARG.  With repair on that call queues one more launch behind the chain's; the published frame carries the
+ * repaired bytes, reports[i].crc_ok is that of the published frame, and every other report field is the decision before repair.           */
+lora_hip_status lora_hip_soft_crc_repair_enable(lora_hip_decoder_t *h, uint32_t candidates);
+
+/* The records of the last lora_hip_soft_decode_at_headers_device call on this handle, one per entry of pre: n must be that call's n (ERR_ARG
+ * otherwise; before any such call: 0).  With repair off every record is NOT_ATTEMPTED.                                                     */
+lora_hip_status lora_hip_soft_crc_repair_results(lora_hip_decoder_t *h, lora_hip_soft_repair_t *out, size_t n);
+
+/* Test and diagnostics entry: the repair kernel alone on n_frames frame bodies given as codewords.  length[f] <= 255: payload bytes in front
+ * of the two CRC bytes; nibble / second (values below 16) / margin: the 2 * (length[f] + 2) body codewords of every frame, back to back;
+ * candidates 1 .. 8.  bytes_out: the length[f] + 2 body bytes of every frame after repair, back to back; records_out: n_frames records.
+ * Host arrays.                                                                                                                              */
+lora_hip_status lora_hip_soft_crc_repair_codewords(lora_hip_decoder_t *h, size_t n_frames, const uint32_t *length, const uint8_t *nibble,
+                                                   const uint8_t *second, const float *margin, uint32_t candidates, uint8_t *bytes_out,
+                                                   lora_hip_soft_repair_t *records_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
